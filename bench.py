@@ -18,9 +18,20 @@ over the ranks by cost bin-packing (shard.assign; "scaling": "strong", the metri
 node at 65k docs"); --scaling weak gives every rank --docs documents of its own instead. No
 data-path collective; RCCL all-gathers per-document digests once, after timing.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--docs D]
-                       [--ops-per-doc O] [--scaling strong|weak] [--assign uniform|cost] [--share R/N]
-                       [--no-cpu-baseline]
+A plain run does what `value` needs and no more: it loads (or generates) the workload, warms up, times the
+steps and prints the line. --full adds the figures that take runs of their own, after timing: `cpu_baseline`
+(the oracle on the host's threads, digests compared with the GPU's) and `end_to_end` (three more replays with
+the host hand-off of the op logs); both are null in a plain run's line. --dump-outputs DIR saves what the last
+timed step left (per-document digests, errors and work counters) as DIR/<name>.npy.
+
+Generating the default workload replays every log on a host model replica (about a minute on 16 threads), so a
+generation that took more than a few seconds is kept under --gen-cache (default: fluidframework_amd/gen under
+the user's cache directory; keyed by the workload and the generator's sources) and later runs memory-map it.
+`python bench.py --prepare` (what __graft_entry__.build() runs where a GPU is present) fills it without a GPU.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--config 1|2|3|4|5]
+                       [--docs D] [--ops-per-doc O] [--scaling strong|weak] [--assign uniform|cost] [--share R/N]
+                       [--no-cpu-baseline] [--no-e2e] [--gen-cache DIR] [--prepare]
 """
 from __future__ import annotations
 
@@ -73,23 +84,75 @@ def workload(config: int, ops: int):
     return {1: gen.config1, 2: gen.config2, 3: gen.config3, 4: gen.config4, 5: gen.config5}[config](ops)
 
 
-def generate_cached(w, ids, cache: str, key: str):
-    """gen.generate, or the same batch memory-mapped from `cache` (written by an earlier run of the
-    same workload on this box: profiler passes re-run the bench several times)."""
+CACHE_MIN_S = 5.0  # a generation quicker than this is not worth a cache entry (the tests' small runs leave none)
+
+
+def default_gen_cache() -> str:
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "fluidframework_amd", "gen")
+
+
+def generator_stamp(w) -> str:
+    """What a generated log depends on besides the document ids: the workload's parameters and the generator's
+    sources (its model replica is the replay core). A change to either makes the cached entries stale."""
+    import hashlib
+    from fluidframework_amd import native
+    h = hashlib.sha256(repr(w).encode())
+    srcs = [os.path.join(native.CSRC, f) for f in ("mt_gen.cpp", "mt_gen.h") + native.CORE_HDRS]
+    for s in srcs + [os.path.join(ROOT, "include", "mt_oplog.h"), os.path.join(ROOT, "fluidframework_amd", "gen.py")]:
+        with open(s, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()[:12]
+
+
+def generate_cached(w, ids, cache: str, key: str, keep: bool = False):
+    """gen.generate, or the same batch memory-mapped from its entry under `cache` (written by an earlier run of
+    the same workload with the same generator). Returns (batch, entry): `entry` is the entry's directory when
+    there is one (cached() keeps values derived from the batch there), else "". A generation that took more than
+    CACHE_MIN_S seconds (or any, with `keep`) is written; a cache that cannot be written is only reported."""
+    import shutil
     import numpy as np
     from fluidframework_amd import gen
     from fluidframework_amd import oplog as ol
     names = [f.name for f in __import__("dataclasses").fields(ol.Batch)]
-    d = os.path.join(cache, key) if cache else ""
+    d = os.path.join(cache, f"{key}-{generator_stamp(w)}") if cache else ""
     if d and os.path.exists(os.path.join(d, "done")):
-        return ol.Batch(*[np.load(os.path.join(d, n + ".npy"), mmap_mode="r") for n in names])
+        return ol.Batch(*[np.load(os.path.join(d, n + ".npy"), mmap_mode="r") for n in names]), d
+    t0 = time.time()
     batch = gen.generate(w, ids=ids, threads=cpu_workers())
-    if d:
-        os.makedirs(d, exist_ok=True)
+    if not d or not (keep or time.time() - t0 > CACHE_MIN_S):
+        return batch, ""
+    tmp = f"{d}.tmp{os.getpid()}"
+    try:
+        os.makedirs(tmp)
         for n in names:
-            np.save(os.path.join(d, n + ".npy"), getattr(batch, n))
-        open(os.path.join(d, "done"), "w").close()
-    return batch
+            np.save(os.path.join(tmp, n + ".npy"), getattr(batch, n))
+        open(os.path.join(tmp, "done"), "w").close()
+        for old in os.listdir(cache):  # entries of this workload from other generator versions
+            if old.startswith(key + "-") and ".tmp" not in old and old != os.path.basename(d):
+                shutil.rmtree(os.path.join(cache, old), ignore_errors=True)
+        os.rename(tmp, d)
+    except OSError as e:
+        log(f"workload cache not written ({e})")
+        shutil.rmtree(tmp, ignore_errors=True)
+        return batch, ""
+    return batch, d
+
+
+def cached(entry: str, name: str, fn):
+    """fn() (a numpy array derived from a generated batch), kept beside the batch in its cache entry."""
+    import numpy as np
+    p = os.path.join(entry, name + ".npy") if entry else ""
+    if p and os.path.exists(p):
+        return np.load(p)
+    v = fn()
+    if p:
+        try:
+            np.save(p + f".tmp{os.getpid()}.npy", v)
+            os.rename(p + f".tmp{os.getpid()}.npy", p)
+        except OSError as e:
+            log(f"workload cache: {name} not written ({e})")
+    return v
 
 
 def cpu_baseline(batch, gpu_digests, workers: int, target_s: float = 15.0):
@@ -131,11 +194,17 @@ def main() -> None:
     ap.add_argument("--docs", type=int, default=0, help="documents per node (strong) or per rank (weak)")
     ap.add_argument("--ops-per-doc", type=int, default=0, help="sequenced messages per document")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
+    ap.add_argument("--full", action="store_true",
+                    help="after timing, also measure the CPU baseline (with its digest comparison) and the end-to-end "
+                         "hand-off runs; a plain run reports neither")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="save what the last timed step computed as DIR/<name>.npy (float64): digests (per document, "
+                         "the 64-bit digest's high and low 32 bits), errors (err, err_op), work (sequenced messages, "
+                         "rows scanned, rows written)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU-baseline threads (default: host share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the end-to-end hand-off runs (profiler passes: their chunked launches would enter the "
-                         "replay kernel's average duration)")
+                    help="with --full: skip the end-to-end hand-off runs")
     ap.add_argument("--digests-out", default="", help="save the per-document digests (.npy) after the run")
     ap.add_argument("--doc-times-out", default="", help="save each document's replay start / end (.npy, 100 MHz ticks)")
     ap.add_argument("--order", choices=("cost", "doc", "measured"), default="doc",
@@ -154,15 +223,20 @@ def main() -> None:
                     help="under torch.distributed.run on a one-GPU box: every rank on device 0, collectives over gloo "
                          "(the multi-rank path of this script end to end on real hardware; not a scaling measurement: "
                          "the ranks share one GPU)")
-    ap.add_argument("--gen-cache", default=os.environ.get("MT_GEN_CACHE", ""),
-                    help="directory caching generated workloads between runs (profiler passes)")
+    ap.add_argument("--gen-cache", default=os.environ.get("MT_GEN_CACHE") or default_gen_cache(),
+                    help="directory caching generated workloads between runs (default: $MT_GEN_CACHE, else "
+                         "fluidframework_amd/gen under the user's cache directory; 'none': no cache)")
+    ap.add_argument("--prepare", action="store_true",
+                    help="generate this command's workload into the cache and exit (no GPU needed)")
     args = ap.parse_args()
+    if args.gen_cache == "none":
+        args.gen_cache = ""
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import numpy as np
-    import torch
 
-    from fluidframework_amd import gen, shard
-    from fluidframework_amd.engine import Engine, default_caps
+    from fluidframework_amd import shard
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -175,7 +249,11 @@ def main() -> None:
     dist = None
     device = 0 if args.rehearse else local_rank
     coll_dev = "cpu" if args.rehearse else f"cuda:{device}"  # where the collectives' tensors live
-    if world > 1 or "LOCAL_WORLD_SIZE" in os.environ:  # under torch.distributed.run: RCCL even for one rank
+    if not args.prepare:  # --prepare only generates: no torch, no engine, no process group
+        import torch
+
+        from fluidframework_amd.engine import Engine, default_caps
+    if not args.prepare and (world > 1 or "LOCAL_WORLD_SIZE" in os.environ):  # under torch.distributed.run: RCCL even for one rank
         import torch.distributed as dist
 
         torch.cuda.set_device(device)
@@ -203,8 +281,9 @@ def main() -> None:
         unit = w.nclients if args.config == 1 else 1
         if args.assign == "cost" and unit == 1:
             # every rank generates the node's logs and packs on shard.doc_costs (deterministic: no exchange)
-            full = generate_cached(w, np.arange(docs), args.gen_cache, f"c{args.config}_d{docs}_o{ops}_all")
-            groups = shard.assign(shard.doc_costs(full), a_world)
+            full, fentry = generate_cached(w, np.arange(docs), args.gen_cache, f"c{args.config}_d{docs}_o{ops}_all",
+                                           keep=args.prepare)
+            groups = shard.assign(cached(fentry, "doc_costs", lambda: shard.doc_costs(full)), a_world)
         else:
             # every document of a config draws the same number of sequenced messages: an even split
             full = None
@@ -216,14 +295,20 @@ def main() -> None:
         mine = shard.weak_ids(rank, docs)
         node_docs = docs * world
     key = f"c{args.config}_d{docs}_o{ops}_{args.scaling}_{args.assign}_r{a_rank}of{a_world}"
-    batch = full.subset(mine) if full is not None else generate_cached(w, mine, args.gen_cache, key)
+    batch, entry = (full.subset(mine), "") if full is not None else generate_cached(w, mine, args.gen_cache, key,
+                                                                                    keep=args.prepare)
     del full
-    log(f"rank {rank}: generated {batch.ndocs} docs, {batch.nops} events in {time.time() - t0:.1f}s")
-    local_events = int(((batch.ops["kind"] & 0x80) != 0).sum())
+    log(f"rank {rank}: {batch.ndocs} docs, {batch.nops} events ready in {time.time() - t0:.1f}s"
+        + (f" (cache entry {entry})" if entry else ""))
+    # two passes over every event record: kept with a cached batch
+    local_events = int(cached(entry, "local_events", lambda: np.array([((batch.ops["kind"] & 0x80) != 0).sum()]))[0])
+    costs = cached(entry, "doc_costs", lambda: shard.doc_costs(batch))
+    if args.prepare:
+        log(f"workload prepared in {entry or '(no cache directory)'}")
+        return
 
     eng = Engine(batch.ndocs, device=device, **default_caps(ops, config=args.config))
     log("engine created")
-    costs = shard.doc_costs(batch)
     if args.order == "cost":  # longest-first list schedule of the documents over the GPU's wave slots
         eng.set_order(np.lexsort((np.arange(batch.ndocs), -costs)).astype(np.int32))
     eng.start_collab(batch.local_long_id)
@@ -281,6 +366,13 @@ def main() -> None:
     # copied through pinned staging buffers); (3) overlapped from pinned memory (a caller that keeps its logs in
     # mt_host_alloc memory: DMA only). Each leaves the same digests as the timed steps.
     ref_digests = eng.digests()
+    if args.dump_outputs:  # the last timed step's results, before anything else replays
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        d_err, d_err_op = eng.errors()
+        outs = {"digests": np.stack([ref_digests >> np.uint64(32), ref_digests & np.uint64(0xFFFFFFFF)], axis=1),
+                "errors": np.stack([d_err, d_err_op], axis=1), "work": work}
+        for name, a in outs.items():  # every value is below 2^53: exact in float64
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float64))
     e2e = {}
 
     def e2e_run(mode, b):
@@ -301,7 +393,7 @@ def main() -> None:
         return t, same
 
     from fluidframework_amd.engine import pinned_batch
-    for mode in () if args.no_e2e else ("serial", "overlapped", "pinned"):
+    for mode in ("serial", "overlapped", "pinned") if args.full and not args.no_e2e else ():
         if mode == "pinned":
             pb, keep = pinned_batch(batch)
             e2e[mode] = e2e_run(mode, pb)
@@ -332,7 +424,7 @@ def main() -> None:
     achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(batch, digests, args.cpu_threads or cpu_workers())
 
     if rank == 0:

@@ -27,6 +27,74 @@ def test_bench_share_of_a_strong_run(assign):
     assert out["value"] > 0
 
 
+SMALL = ["--config", "3", "--docs", "96", "--ops-per-doc", "512", "--steps", "2", "--warmup", "1"]
+
+
+def _bench(*extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(extra), capture_output=True, text=True,
+                       timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r
+
+
+def test_bench_prepare_fills_the_workload_cache(tmp_path):
+    """--prepare needs no GPU: it writes the workload's cache entry (keyed by the workload and the generator's
+    sources) with the values derived from it, and a second call finds that entry instead of writing another."""
+    import numpy as np
+
+    from fluidframework_amd import gen
+    cache = str(tmp_path / "gen")
+    _bench(*SMALL, "--prepare", "--gen-cache", cache)
+    entries = os.listdir(cache)
+    assert len(entries) == 1 and entries[0].startswith("c3_d96_o512_strong_uniform_r0of1-")
+    d = os.path.join(cache, entries[0])
+    b = gen.generate(gen.config3(512), ids=np.arange(96))
+    assert np.array_equal(np.load(os.path.join(d, "ops.npy")), b.ops)
+    assert np.array_equal(np.load(os.path.join(d, "op_off.npy")), b.op_off)
+    assert int(np.load(os.path.join(d, "local_events.npy"))[0]) == int(((b.ops["kind"] & 0x80) != 0).sum())
+    stamp = os.path.getmtime(os.path.join(d, "ops.npy"))
+    _bench(*SMALL, "--prepare", "--gen-cache", cache)
+    assert os.listdir(cache) == entries and os.path.getmtime(os.path.join(d, "ops.npy")) == stamp
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain run measures the headline figure only (cpu_baseline and end_to_end are null) and --dump-outputs
+    saves the last timed step's per-document results as float64: the digests are the oracle's for the same logs,
+    and a run from the cached workload dumps the same arrays."""
+    import numpy as np
+
+    import oracle_client as oc
+    from fluidframework_amd import gen
+    cache = str(tmp_path / "gen")
+    _bench(*SMALL, "--prepare", "--gen-cache", cache)
+    outs = []
+    for run, cache_arg in (("a", cache), ("b", "none")):
+        r = _bench(*SMALL, "--gen-cache", cache_arg, "--dump-outputs", str(tmp_path / run))
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["cpu_baseline"] is None and line["end_to_end"] is None
+        assert line["config"]["docs_in_error_rank0"] == 0
+        outs.append({n: np.load(str(tmp_path / run / (n + ".npy"))) for n in ("digests", "errors", "work")})
+        assert all(a.dtype == np.float64 and a.shape[0] == 96 for a in outs[-1].values())
+    for n in outs[0]:
+        assert np.array_equal(outs[0][n], outs[1][n]), n
+    b = gen.generate(gen.config3(512), ids=np.arange(96))
+    _, odig, oerr = oc.replay_batch(b, threads=4)
+    assert (oerr == 0).all() and (outs[0]["errors"][:, 0] == 0).all()  # column 1 is the failing event (-1: none)
+    d = outs[0]["digests"].astype(np.uint64)
+    assert np.array_equal((d[:, 0] << np.uint64(32)) | d[:, 1], odig)
+    assert outs[0]["work"][:, 0].sum() == 96 * 512  # every sequenced message applied
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_cpu_baseline_and_the_end_to_end_runs():
+    line = json.loads(_bench(*SMALL, "--gen-cache", "none", "--full").stdout.strip().splitlines()[-1])
+    assert line["cpu_baseline"]["value"] > 0 and "digests match GPU: True" in line["cpu_baseline"]["sample"]
+    modes = line["end_to_end"]["modes"]
+    assert sorted(modes) == ["overlapped", "pinned", "serial"] and all(m["digests_equal"] for m in modes.values())
+
+
 @pytest.mark.gpu
 def test_bench_two_rank_rehearsal_on_one_gpu():
     """The multi-rank path of bench.py end to end on real hardware: torch.distributed.run with two ranks, both on

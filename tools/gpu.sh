@@ -6,7 +6,7 @@
 # Steps (run in order; every GPU step has its own time limit and the chain stops at the first failure):
 #   tests[=EXPR]     pytest -m gpu (optionally -k EXPR)            -> OUT/pytest_gpu.txt
 #   smoke            __graft_entry__ smoke()                        -> OUT/smoke.txt
-#   bench:C          bench.py --config C (with CPU baseline)        -> OUT/bench_cC.json
+#   bench:C          bench.py --config C --full (CPU baseline, e2e) -> OUT/bench_cC.json
 #   trace:C          rocprofv3 --kernel-trace --stats of bench.py   -> OUT/trace_cC/ (+ kernel_stats.csv)
 #   traffic:C        FETCH_SIZE pass + WRITE_SIZE pass              -> OUT/pmc_fetch_cC, OUT/pmc_write_cC
 #   inst:C           SQ instruction-count pass                      -> OUT/pmc_inst_cC
@@ -48,7 +48,7 @@ for S in "$@"; do
       timeout -k 10 300 python -u __graft_entry__.py smoke > "$OUT/smoke.txt" 2>&1 || fail "$S" $? "$OUT/smoke.txt"
       tail -1 "$OUT/smoke.txt" ;;
     bench)
-      timeout -k 10 $(prof_lim "$A") python -u bench.py $(bargs "$A") > "$OUT/bench_c$A.json" 2> "$OUT/bench_c$A.err" \
+      timeout -k 10 $(prof_lim "$A") python -u bench.py $(bargs "$A") --full > "$OUT/bench_c$A.json" 2> "$OUT/bench_c$A.err" \
         || fail "$S" $? "$OUT/bench_c$A.err"
       cat "$OUT/bench_c$A.json" ;;
     trace)

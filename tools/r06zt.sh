@@ -6,7 +6,7 @@ export TMPDIR=/tmp MT_GEN_CACHE=/tmp/mtgen
 OUT=gpurun_out/r06zt
 mkdir -p $OUT
 for t in 0 1 0 1; do
-  MT_SUBMIT_RAMP=$t timeout -k 10 420 python -u bench.py --config 3 --no-cpu-baseline > $OUT/e2e_ramp$t.json 2> $OUT/e2e_ramp$t.err \
+  MT_SUBMIT_RAMP=$t timeout -k 10 420 python -u bench.py --config 3 --full --no-cpu-baseline > $OUT/e2e_ramp$t.json 2> $OUT/e2e_ramp$t.err \
     || { tail -20 $OUT/e2e_ramp$t.err; exit 1; }
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); e=d['end_to_end']; print('ramp', sys.argv[2], round(d['value']/1e6,1), 'kernel', {k: (round(v['value']/1e6,1), v['digests_equal']) for k, v in e['modes'].items()})" $OUT/e2e_ramp$t.json $t
   cp $OUT/e2e_ramp$t.json $OUT/e2e_ramp${t}_$(date +%s).json
