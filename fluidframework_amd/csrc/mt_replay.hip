@@ -1137,6 +1137,7 @@ int32_t mt_engine_delta_state(mt_engine* e, int64_t* n_out, uint64_t* hash_out) 
 
 int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
     if (!e || e->dcap <= 0 || doc < 0 || doc >= e->ndocs || cap < 0) return -MT_E_ARG;
+    const int64_t dcap = e->dcap; /* the caller's engine's: a promoted document's engine logs four times as many */
     e = route(e, &doc);
     if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
     int64_t off, stride;
@@ -1145,7 +1146,7 @@ int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
     DState st;
     if (hipMemcpyAsync(&st, base, sizeof st, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    int64_t logged = st.n < e->dcap ? st.n : e->dcap;
+    int64_t logged = st.n < dcap ? st.n : dcap;
     int64_t m = logged < cap ? logged : cap;
     if (out && m > 0) {
         if (hipMemcpyAsync(out, base + sizeof(DState), 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
@@ -1229,10 +1230,15 @@ int32_t mt_engine_ref_positions(mt_engine* e, int32_t* nref_out, int32_t* pos_ou
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (promoted(e)) {
         size_t m = e->pro_docs.size();
-        std::vector<int32_t> a(m), b(m * (size_t)e->rcap);
-        if ((rc = mt_engine_ref_positions(e->over, a.data(), b.data()))) return rc;
+        /* the promoted engine's rows have its own (larger) length; the caller's rows keep e->rcap entries, the
+         * first of each child row. nref stays the true count (it may exceed e->rcap). */
+        size_t crow = (size_t)mt_engine_ref_capacity(e->over), row = (size_t)e->rcap;
+        std::vector<int32_t> a(m), b(m * crow);
+        if ((rc = mt_engine_ref_positions(e->over, a.data(), pos_out ? b.data() : nullptr))) return rc;
         if (nref_out) scatter(nref_out, a, e->pro_docs, 1);
-        if (pos_out) scatter(pos_out, b, e->pro_docs, e->rcap);
+        if (pos_out)
+            for (size_t i = 0; i < m; i++)
+                std::copy_n(b.data() + i * crow, std::min(row, crow), pos_out + (size_t)e->pro_docs[i] * row);
     }
     return MT_OK;
 }

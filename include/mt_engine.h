@@ -234,7 +234,10 @@ int32_t mt_engine_delta_state(mt_engine* e, int64_t* n_out, uint64_t* hash_out);
 int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap);
 /* Local references (MT_OP_REF records; engines created with caps.rcap > 0): per doc the number of
  * references (nref_out[d]) and, for reference i, LocalReference.toPosition() (localReference.ts:62-68:
- * Client.getPosition(segment) + getOffset(), -1 when detached) at pos_out[d * rcap + i]. References
+ * Client.getPosition(segment) + getOffset(), -1 when detached) at pos_out[d * rcap + i]; the row length is
+ * caps.rcap of the engine the caller created, for promoted documents too: a promoted document's row holds its
+ * first rcap references, and nref_out[d] is its true count, which exceeds rcap when the document was promoted
+ * because it ran out of reference slots (entries of a row past min(nref, rcap) are unspecified). References
  * follow their segment through splits and zamboni appends, and a remove slides SlideOnRemove ones to
  * the next (or last) segment and detaches the rest (mergeTree.ts:2703-2732, localReference.ts:
  * 251-342). -2: the reference's Client.addLocalReference threw for this reference (its offset holds

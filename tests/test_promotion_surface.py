@@ -1,0 +1,463 @@
+"""Every per-document read of the C ABI (include/mt_engine.h) across capacity promotion.
+
+A document that latches MT_E_CAPACITY replays again in an engine of the next profile, and "every per-document call
+... then answers for them from there" (mt_engine_sync). Through every entry point a promoted document must be
+indistinguishable from the same document in an engine created directly at the larger profile, and both must equal
+the CPU spec: the host build of the engine core (tests/core_host.py, pinned to the reference elsewhere in the
+suite) and, for text, lengths and segment queries, the oracle (tests/oracle_client.py). No expected value comes
+from the GPU engine.
+
+Batches (tests/promotion_mix.py): text_mix holds ten config-3 documents and three coalescing-defeated config-4
+documents at indices 1, 4 and 12; two of those leave the small profile only (-> 2,048 nodes) and the one at index
+4 leaves the 2,048-node profile too (-> 16,384 nodes: a third engine). perm_mix holds config-5 documents with
+getAllocatedHandle records, two of them too long for the 640-node profile. The CPU tier pins which documents
+latch at which capacities; every GPU test asserts the same set was promoted.
+
+Engine A is created at the starting capacities (promotion happens), engines B directly at the capacities the
+promoted documents end in (B_mid: 2,048 nodes, where only the chain document is promoted once more; B_big: 16,384
+nodes, nothing promoted). Before the fix that came with this module mt_engine_ref_positions read the promoted
+engine's rows (4x the caller's row length) into a buffer sized for the caller's, and mt_engine_deltas returned up
+to 4x dcap words for a promoted document; the reference-position and delta tests here would have met both."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from fluidframework_amd import gen
+from fluidframework_amd import oplog as ol
+import core_host
+import oracle_client as oc
+import persp_logs as pl
+import promotion_mix as pm
+
+E_UNSUPPORTED, E_CAPACITY = 4, 5
+RCAP, DCAP = 32, 4096
+REMOTE = (2, 5, 7)  # long client ids of three remote clients (the generated replicas are client 1)
+
+
+# ---- fixtures (CPU) ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def text_mix():
+    return pm.text_mix()
+
+
+@pytest.fixture(scope="module")
+def text_refs(text_mix):
+    return pm.text_refs(text_mix)
+
+
+@pytest.fixture(scope="module")
+def text_spec(text_refs):
+    """the host core over text_refs at the 16,384-node capacities: (digests, store)"""
+    dig, err, st = core_host.replay_batch(text_refs, pm.tup(pm.BIG), dcap=DCAP, rcap=RCAP)
+    assert (err == 0).all()
+    return dig, st
+
+
+@pytest.fixture(scope="module")
+def text_oracle(text_mix):
+    out = []
+    for d in range(text_mix.ndocs):
+        c = oc.OracleClient()
+        c.start_collab(int(text_mix.local_long_id[d]))
+        assert c.replay_arrays(*text_mix.doc(d)) == 0
+        out.append(c)
+    return out
+
+
+@pytest.fixture(scope="module")
+def perm_mix():
+    return pm.perm_mix()
+
+
+def latched(err):
+    return set(np.nonzero(err == E_CAPACITY)[0].tolist())
+
+
+# ---- CPU tier: the construction ---------------------------------------------------------------------------------
+def test_text_mix_overflows_where_intended(text_mix, text_refs):
+    assert text_mix.ndocs == pm.NSMALL + 3
+    for b in (text_mix, text_refs):
+        _, e_small, _ = core_host.replay_batch(b, pm.tup(pm.SMALL), rcap=RCAP)
+        _, e_mid, _ = core_host.replay_batch(b, pm.tup(pm.MID), rcap=RCAP)
+        _, e_big, _ = core_host.replay_batch(b, pm.tup(pm.BIG), rcap=RCAP)
+        assert latched(e_small) == pm.TEXT_PROMOTED and set(e_small.tolist()) == {0, E_CAPACITY}
+        assert latched(e_mid) == {pm.TEXT_CHAIN} and set(e_mid.tolist()) == {0, E_CAPACITY}
+        assert (e_big == 0).all()
+    # the lengths are the smallest that overflow: one op fewer fits, and the high-water marks are the module's
+    for (did, n), caps, nodes, slots in ((pm.MID_A, pm.SMALL, 192, 1224), (pm.MID_B, pm.SMALL, 192, 1224),
+                                         ((pm.CHAIN[0], pm.CHAIN_SMALL_OPS), pm.SMALL, 192, 1232),
+                                         (pm.CHAIN, pm.MID, 2048, 13080)):
+        _, e1, st = core_host.replay_batch(gen.generate(gen.config4(n), ids=[did], threads=1), pm.tup(caps))
+        _, e0, _ = core_host.replay_batch(gen.generate(gen.config4(n - 1), ids=[did], threads=1), pm.tup(caps))
+        assert (int(e1[0]), int(e0[0])) == (E_CAPACITY, 0), (did, n)
+        s = st.stats(0)
+        assert (s["nodes"], s["hw_slots"]) == (nodes, slots), (did, n, s)
+    # every document holds its 24 references, so 8 reference slots overflow on every document
+    _, e8, _ = core_host.replay_batch(text_refs, pm.tup(pm.BIG), rcap=8)
+    assert (e8 == E_CAPACITY).all()
+    # the second batch's longer logs extend text_mix's and fit where their documents end
+    for (d, whole), caps in zip(pm.text_tails(), (pm.SMALL, pm.MID)):
+        ops = text_mix.doc_arrays(d)[0]
+        assert len(whole[0]) > len(ops) and np.array_equal(whole[0][: len(ops)], ops)
+        _, e, _ = core_host.replay_batch(ol.Batch.from_arrays([whole], text_mix.local_long_id[[d]]), pm.tup(caps))
+        assert e[0] == 0
+
+
+def test_perm_mix_overflows_where_intended(perm_mix):
+    _, e_mat, st_mat = core_host.replay_batch(perm_mix, pm.tup(pm.MAT), pcap=pm.PCAP)
+    _, e_mid, st = core_host.replay_batch(perm_mix, pm.tup(pm.MAT_MID), pcap=pm.PCAP)
+    assert latched(e_mat) == pm.PERM_PROMOTED and set(e_mat.tolist()) == {0, E_CAPACITY}
+    assert (e_mid == 0).all()
+    for d in range(perm_mix.ndocs):  # handles are allocated in every document
+        assert (st.handle_table(d)[1:] == 0).any(), d
+    for at, s in ((1, (640, 4144)), (4, (640, 4104))):  # the module's high-water marks
+        assert (st_mat.stats(at)["nodes"], st_mat.stats(at)["hw_slots"]) == s, (at, st_mat.stats(at))
+    # one op fewer in both long documents (their handle records drawn anew): nothing latches
+    shorter = pm.perm_mix({at: (did, n - 1) for at, (did, n) in pm.PERM_AT.items()})
+    assert (core_host.replay_batch(shorter, pm.tup(pm.MAT), pcap=pm.PCAP)[1] == 0).all()
+
+
+def test_incr_document_needs_promotion_and_value_kinds():
+    log = pm.incr_log()
+    b = ol.Batch.from_logs([log])
+    kinds = ol.value_kinds(log.interner)
+    assert core_host.replay_batch(b, pm.tup(pm.SMALL), kinds=kinds)[1][0] == E_CAPACITY  # 14 keys, 8 key slots
+    assert core_host.replay_batch(b, pm.tup(pm.MID))[1][0] == E_UNSUPPORTED  # no value kinds
+    _, err, st = core_host.replay_batch(b, pm.tup(pm.MID), kinds=kinds)
+    assert err[0] == 0
+    _, segs = ol.parse_dump(st.dump(0))
+    assert any(isinstance(v, ol.Derived) and v.kind == "strcat" for s in segs for _, v in s["props"])
+
+
+# ---- GPU tier ---------------------------------------------------------------------------------------------------
+def _engine(b, caps, **fx):
+    from fluidframework_amd.engine import Engine
+    eng = Engine(b.ndocs, **caps, **fx)
+    eng.start_collab(b.local_long_id)
+    return eng
+
+
+def _clean(eng, promoted):
+    err, err_op = eng.errors()
+    assert (err == 0).all(), (err, err_op)
+    assert set(eng.promoted().tolist()) == set(promoted)
+
+
+@pytest.fixture(scope="module")
+def trio(text_refs):
+    """text_refs replayed in A (small profile), B_mid and B_big, each with 32 reference slots and 4,096 delta words"""
+    engs = []
+    for caps in (pm.SMALL, pm.MID, pm.BIG):
+        eng = _engine(text_refs, caps, rcap=RCAP, dcap=DCAP)
+        eng.replay(text_refs)
+        engs.append(eng)
+    yield engs
+    for eng in engs:
+        eng.close()
+
+
+def _check_trio(trio):
+    a, b_mid, b_big = trio
+    _clean(a, pm.TEXT_PROMOTED)
+    _clean(b_mid, {pm.TEXT_CHAIN})  # so in A the chain document answers from a third engine
+    _clean(b_big, ())
+
+
+def _b_for(trio, d):
+    """the engine that holds document d, unpromoted, at the profile it ends in in A"""
+    return trio[2] if d == pm.TEXT_CHAIN else trio[1]
+
+
+def _raw_ref_positions(eng, guard=4096):
+    """mt_engine_ref_positions into a buffer with a guard behind the ndocs * rcap words it may write"""
+    sent = -777777
+    n = np.zeros(eng.ndocs, np.int32)
+    pos = np.full(eng.ndocs * eng.caps.rcap + guard, sent, np.int32)
+    vp = ctypes.c_void_p
+    assert eng.L.mt_engine_ref_positions(eng.h, n.ctypes.data_as(vp), pos.ctypes.data_as(vp)) == 0
+    assert (pos[eng.ndocs * eng.caps.rcap:] == sent).all(), "wrote past the caller's rows"
+    return n, pos[: eng.ndocs * eng.caps.rcap].reshape(eng.ndocs, eng.caps.rcap)
+
+
+@pytest.mark.gpu
+def test_gpu_local_references_of_promoted_documents(trio, text_mix, text_refs, text_spec):
+    _check_trio(trio)
+    dig, st = text_spec
+    _, odig, oerr = oc.replay_batch(text_mix, threads=4)
+    assert (oerr == 0).all() and np.array_equal(dig, odig)  # the references change no replica
+    want = [st.ref_positions(d) for d in range(text_refs.ndocs)]
+    assert all(len(w) == 24 for w in want)
+    for name, eng in zip(("A", "B_mid", "B_big"), trio):
+        assert np.array_equal(eng.digests(), dig), name
+        nref, pos = _raw_ref_positions(eng)
+        for d in range(text_refs.ndocs):
+            assert nref[d] == len(want[d]), (name, d)
+            assert np.array_equal(pos[d, : nref[d]], want[d]), (name, d)
+    # 8 reference slots: every document runs out of them and is promoted for that alone (the large ones twice or
+    # three times); nref is the true count, a row holds the first 8 positions
+    a8 = _engine(text_refs, pm.SMALL, rcap=8)
+    a8.replay(text_refs)
+    _clean(a8, range(text_refs.ndocs))
+    assert np.array_equal(a8.digests(), dig)
+    nref, pos = _raw_ref_positions(a8)
+    for d in range(text_refs.ndocs):
+        assert nref[d] == len(want[d]), d
+        assert np.array_equal(pos[d], want[d][:8]), d
+    a8.close()
+
+
+@pytest.mark.gpu
+def test_gpu_delta_events_of_promoted_documents(trio, text_refs, text_spec):
+    """also the first run of the delta-event build of the 2,048-node profile (B_mid, and A's promoted engine)"""
+    _check_trio(trio)
+    _, st = text_spec
+    want = [st.deltas(d) for d in range(text_refs.ndocs)]
+    assert all(w[0] > DCAP for w in want)  # every log is cut short at the caller's dcap
+    for name, eng in zip(("A", "B_mid", "B_big"), trio):
+        n, h = eng.delta_state()
+        for d in range(text_refs.ndocs):
+            wn, wh, words = want[d]
+            words = words[: min(wn, DCAP)]  # the host core logged that many (its dcap is the caller's)
+            assert (int(n[d]), int(h[d])) == (wn, wh), (name, d)
+            got = eng.deltas(d)
+            assert len(got) == min(wn, DCAP), (name, d)
+            assert np.array_equal(got, words), (name, d)
+            # a shorter buffer: the same count, the first words only, nothing behind them
+            buf = np.full(64, -1, np.int32)
+            assert eng.L.mt_engine_deltas(eng.h, d, buf.ctypes.data_as(ctypes.c_void_p), 48) == min(wn, DCAP)
+            assert np.array_equal(buf[:48], words[:48]) and (buf[48:] == -1).all(), (name, d)
+
+
+@pytest.mark.gpu
+def test_gpu_delta_events_tiled_profile():
+    """the delta-event build of the tiled profile: counts, hashes and logged words equal the host core's"""
+    from fluidframework_amd.engine import default_caps
+    caps = default_caps(2048, config=4)
+    dcap = 1 << 15
+    b = gen.generate(gen.config3(2048), ids=np.arange(4), threads=4)
+    _, err, st = core_host.replay_batch(b, pm.tup(caps), dcap=dcap)
+    assert (err == 0).all()
+    eng = _engine(b, caps, dcap=dcap)
+    eng.replay(b)
+    _clean(eng, ())
+    n, h = eng.delta_state()
+    for d in range(b.ndocs):
+        wn, wh, words = st.deltas(d)
+        assert wn > dcap and (int(n[d]), int(h[d])) == (wn, wh), d
+        assert np.array_equal(eng.deltas(d), words[:dcap]), d
+    eng.close()
+
+
+@pytest.mark.gpu
+def test_gpu_handles_of_promoted_documents(perm_mix):
+    from fluidframework_amd.engine import EngineError
+    _, err, st = core_host.replay_batch(perm_mix, pm.tup(pm.MAT_MID), pcap=pm.PCAP)
+    assert (err == 0).all()
+    a = _engine(perm_mix, pm.MAT, pcap=pm.PCAP)
+    b = _engine(perm_mix, pm.MAT_MID, pcap=pm.PCAP)
+    for eng, promoted in ((a, pm.PERM_PROMOTED), (b, ())):
+        eng.replay(perm_mix)
+        _clean(eng, promoted)
+    for d in range(perm_mix.ndocs):
+        assert a.digests()[d] == b.digests()[d] == st.digest(d), d
+        table = st.handle_table(d)
+        hdr, _ = ol.parse_dump(st.dump(d))
+        length = st.length_local(d)
+        assert hdr["length"] == length
+        where = {}  # allocated handle -> its local position (HandleCache.getHandle of every position)
+        for p in range(length):
+            hd = st.get_handle(d, p)
+            if hd != ol.HANDLE_UNALLOCATED:
+                where[hd] = p
+        assert where, d
+        for name, eng in (("A", a), ("B", b)):
+            assert np.array_equal(eng.handle_table(d), table), (name, d)
+            assert eng.get_length(d) == length, (name, d)
+            for p in range(0, length, 10):
+                assert eng.get_handle(d, p) == st.get_handle(d, p), (name, d, p)
+        for hd in (i for i in range(1, len(table)) if table[i] == 0):  # every allocated handle
+            got = []
+            for eng in (a, b):
+                try:
+                    got.append(eng.handle_to_position(d, hd, hdr["localSeq"]))
+                except EngineError as ex:  # its segment left the tree: the reference asserts too
+                    got.append(("refused", ex.code))
+            assert got[0] == got[1], (d, hd, got)
+            if hd in where:  # at the current localSeq the reconnection position is the local position
+                assert got[0] == where[hd], (d, hd, got)
+    a.close()
+    b.close()
+
+
+def _visible(seg, ref, k):
+    """the leaf visibility of a dump record under (refSeq, long client k); k None = the local view"""
+    rs = seg["removedSeq"]
+    if k is None:
+        return rs is None
+    if seg["seq"] < 0 or not (seg["seq"] <= ref or seg["client"] == k):
+        return False
+    return not (rs is not None and rs >= 0 and (rs <= ref or seg["removedClient"] == k or k in seg["overlap"]))
+
+
+def _resolve_remote(segs, pos, ref, k):
+    """MergeTree.resolveRemoteClientPosition (mergeTree.ts:2140-2160) over the oracle's dump"""
+    seen = local = 0
+    for s in segs:
+        if _visible(s, ref, k) and pos < seen + s["len"]:
+            return local + pos - seen  # getPosition(segment) in the local view + offset
+        seen += s["len"] if _visible(s, ref, k) else 0
+        local += s["len"] if _visible(s, None, None) else 0
+    return local if pos == seen else None
+
+
+def _try(f):
+    from fluidframework_amd.engine import EngineError
+    try:
+        return f()
+    except EngineError as ex:
+        return ("refused", ex.code)
+
+
+@pytest.mark.gpu
+def test_gpu_reads_of_promoted_documents(trio, text_mix, text_refs, text_oracle, text_spec):
+    _check_trio(trio)
+    a = trio[0]
+    _, st = text_spec
+    err, err_op = a.errors()
+    stats = [e.stats() for e in trio]
+    work = [e.work() for e in trio]
+    answered = refused = 0
+    for d in sorted(pm.TEXT_PROMOTED) + [0, 7]:
+        b = _b_for(trio, d)
+        bi = trio.index(b)
+        c = text_oracle[d]
+        ops = text_mix.doc(d)[0]
+        local = int(text_mix.local_long_id[d])
+        n, text = c.get_length(), c.get_text()
+        hdr, segs = ol.parse_dump(c.dump())
+        assert sum(s["len"] for s in segs if _visible(s, None, None)) == n
+        for name, eng in (("A", a), ("B", b)):
+            tag = (name, d)
+            assert eng.dump(d) == c.dump(), tag
+            assert eng.get_length(d) == n and eng.get_text(d) == text, tag
+            assert len(eng.segment_ids(d)) == hdr["nsegs"] == len(segs), tag
+            assert eng.doc_error(d) == (int(err[d]), int(err_op[d])) == (0, -1), tag
+            lo, hi = n // 3, 2 * n // 3
+            assert eng.get_text(d, placeholder="##", start=lo, end=hi) == st.text_range(d, 0, -1, "##", lo, hi), tag
+            for pos in (0, n // 2, n - 1, n):
+                s = eng.get_containing_segment(d, pos)
+                want = c.containing(pos)
+                assert (s is not None) == bool(want[0]) == (pos < n), (tag, pos)
+                if s is not None:
+                    assert (s.offset, s.length, s.seq, s.client) == want[1:5], (tag, pos)
+                    assert eng.get_position(d, s) + s.offset == pos == want[5] + want[1], (tag, pos)
+                    assert (segs[s.ordinal]["len"], segs[s.ordinal]["seq"]) == (s.length, s.seq), (tag, pos)
+        cur = c.current_seq
+        assert cur == pl.window(ops)[0]
+        for ref in (cur, cur - 5, pl.window(ops)[1] - 1):  # the last: below minSeq, refused for every remote client
+            for k in REMOTE:
+                ga = _try(lambda: (a.get_length(d, ref, k), a.get_text(d, ref, k)))
+                gb = _try(lambda: (b.get_length(d, ref, k), b.get_text(d, ref, k)))
+                if not pl.answered(ops, local, ref, k):
+                    assert ga == gb == ("refused", E_UNSUPPORTED), (d, ref, k, ga, gb)
+                    assert _try(lambda: a.resolve_remote_client_position(d, 0, ref, k)) == ga, (d, ref, k)
+                    refused += 1
+                    continue
+                want_n = c.get_length_at(ref, k)
+                assert ga == gb == (want_n, c.get_text_at(ref, k)), (d, ref, k)
+                assert sum(s["len"] for s in segs if _visible(s, ref, k)) == want_n, (d, ref, k)
+                for pos in (0, want_n // 2, want_n - 1, want_n, want_n + 1):
+                    want = _resolve_remote(segs, pos, ref, k)
+                    for name, eng in (("A", a), ("B", b)):
+                        assert eng.resolve_remote_client_position(d, pos, ref, k) == want, (name, d, ref, k, pos)
+                answered += 1
+        # the same kernel over the same log: the same counters (events applied: every record of the log)
+        if d in pm.TEXT_PROMOTED:
+            assert np.array_equal(stats[0][d], stats[bi][d]), (d, stats[0][d], stats[bi][d])
+            assert np.array_equal(work[0][d], work[bi][d]), (d, work[0][d], work[bi][d])
+            assert stats[0][d][3] == len(text_refs.doc(d)[0]), d
+    assert answered >= 10 and refused >= 1, (answered, refused)
+
+
+def _host_digests(b, caps_of, kinds=None):
+    """host-core digests of every document, each at the capacities caps_of(d)"""
+    out = np.zeros(b.ndocs, np.uint64)
+    for d in range(b.ndocs):
+        dig, err, _ = core_host.replay_batch(b.subset([d]), pm.tup(caps_of(d)), kinds=kinds)
+        assert err[0] == 0, d
+        out[d] = dig[0]
+    return out
+
+
+def _text_caps(d):
+    return pm.BIG if d == pm.TEXT_CHAIN else pm.MID if d in pm.TEXT_PROMOTED else pm.SMALL
+
+
+@pytest.mark.gpu
+def test_gpu_ways_into_promotion(text_mix):
+    from fluidframework_amd.engine import MT_VAR_CHUNK_DOCS
+    want = _host_digests(text_mix, _text_caps)
+    # chunked hand-off: the promoted documents fall in different chunks; then the staged batch again
+    eng = _engine(text_mix, pm.SMALL)
+    eng.set_variant(MT_VAR_CHUNK_DOCS, 3)
+    eng.submit_run(text_mix)
+    eng.sync()
+    _clean(eng, pm.TEXT_PROMOTED)
+    assert np.array_equal(eng.digests(), want)
+    eng.reset()
+    eng.run()
+    eng.sync()
+    _clean(eng, pm.TEXT_PROMOTED)
+    assert np.array_equal(eng.digests(), want)
+    eng.close()
+    # a dispatch order
+    eng = _engine(text_mix, pm.SMALL)
+    eng.set_order(np.arange(text_mix.ndocs)[::-1])
+    eng.replay(text_mix)
+    _clean(eng, pm.TEXT_PROMOTED)
+    assert np.array_equal(eng.digests(), want)
+    # a second batch on top, for one unpromoted and one promoted document: the promoted one's records replay in
+    # the promoted engine, on top of the state it holds
+    eng.set_order(None)
+    tails = pm.text_tails()
+    docs = [d for d, _ in tails]
+    assert docs == [0, 1] and 1 in pm.TEXT_PROMOTED
+    arrays = []
+    for d, (ops, text, props, kv) in tails:
+        cut = len(text_mix.doc(d)[0])
+        assert not ops["kind"][cut - 1] & ol.OPF_GROUPED  # a record boundary that splits no group
+        arrays.append((ops[cut:], text, props, kv))
+    eng.submit_docs(docs, ol.Batch.from_arrays(arrays, text_mix.local_long_id[docs]))
+    eng.run()
+    eng.sync()
+    _clean(eng, pm.TEXT_PROMOTED)
+    got = eng.digests()
+    whole = ol.Batch.from_arrays([w for _, w in tails], text_mix.local_long_id[docs])
+    tail_want = _host_digests(whole, lambda i: _text_caps(docs[i]))
+    assert (tail_want != want[docs]).all()  # the second batch changed both documents
+    for d in range(text_mix.ndocs):
+        assert got[d] == (tail_want[docs.index(d)] if d in docs else want[d]), d
+    assert eng.doc_error(1) == (0, -1)
+    eng.close()
+
+
+@pytest.mark.gpu
+def test_gpu_promoted_document_keeps_value_kinds(text_mix):
+    """an "incr" annotate over an interned string in a document promoted for its property keys: the promoted engine
+    gets the value kinds (without them the document would latch MT_E_UNSUPPORTED there). The oracle does not model
+    incr, so the dump is the host core's (pinned to the reference in tests/test_ref_combine.py)."""
+    log = pm.incr_log()
+    at = 7
+    b = pm.text_mix(extra=(at, log.arrays(), log.local_long_id))
+    kinds = ol.value_kinds(log.interner)
+    _, err, st = core_host.replay_batch(b.subset([at]), pm.tup(pm.MID), kinds=kinds)
+    assert err[0] == 0
+    eng = _engine(b, pm.SMALL)
+    eng.set_value_kinds(kinds)
+    eng.replay(b)
+    _clean(eng, {1, 4, at, 13})
+    assert eng.doc_error(at) == (0, -1)
+    assert eng.dump(at) == st.dump(0)
+    assert eng.digests()[at] == st.digest(0)
+    eng.close()
