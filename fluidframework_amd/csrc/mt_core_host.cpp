@@ -20,12 +20,7 @@ using namespace mt;
 struct mth_store {
     int profile;
     int64_t ndocs;
-    Store<HotSmall> s0;
-    Store<HotMid> s1;
-    Store<HotBig> s2;
-    Store<HotMat> s3;
-    Store<HotHuge> s4;
-    uint8_t* mem;
+    AnyStore st;    /* st.base: host_store_alloc */
     uint8_t* vkind; /* value kinds (mth_set_value_kinds; mt_engine_set_value_kinds) */
     int32_t nvk;
 };
@@ -33,32 +28,13 @@ struct mth_store {
 /* call F with a Replica<WaveHost, HT, true> (delta events on) for doc d of the store's profile */
 template <class F>
 static auto with_replica(mth_store* s, int64_t d, F&& f) {
-    /* every call ends with commit(): the replica's register header goes back to the image */
-    if (s->profile == 0) {
-        Replica<WaveHost, HotSmall, true> r(s->s0.doc(d), WaveHost());
+    return with_profile(s->profile, [&](auto tag) {
+        typedef typename decltype(tag)::Hot HT;
+        Replica<WaveHost, HT, true> r(s->st.as<HT>().doc(d), WaveHost());
         auto res = f(r);
-        r.commit();
+        r.commit(); /* every call ends here: the replica's register header goes back to the image */
         return res;
-    } else if (s->profile == 3) {
-        Replica<WaveHost, HotMat, true> r(s->s3.doc(d), WaveHost());
-        auto res = f(r);
-        r.commit();
-        return res;
-    } else if (s->profile == 1) {
-        Replica<WaveHost, HotMid, true> r(s->s1.doc(d), WaveHost());
-        auto res = f(r);
-        r.commit();
-        return res;
-    } else if (s->profile == 4) {
-        Replica<WaveHost, HotHuge, true> r(s->s4.doc(d), WaveHost());
-        auto res = f(r);
-        r.commit();
-        return res;
-    }
-    Replica<WaveHost, HotBig, true> r(s->s2.doc(d), WaveHost());
-    auto res = f(r);
-    r.commit();
-    return res;
+    });
 }
 
 extern "C" {
@@ -78,22 +54,17 @@ mth_store* mth_create_fx2(int64_t ndocs, const int32_t* caps6, int32_t dcap, int
      * log words per doc (mt_caps.dcap); rcap: local references per doc (mt_caps.rcap); pcap:
      * PermutationVector handles per doc (mt_caps.pcap) */
     Caps k = {caps6[2], caps6[3], caps6[4], dcap < 0 ? 0 : dcap, rcap < 0 ? 0 : rcap, pcap < 0 ? 0 : pcap};
-    int prof = profile_for(caps6[0]);
-    if (!caps_valid(k) || ndocs < 1 || prof < 0) return nullptr;
+    Profile prof = profile_for(caps6[0]);
+    if (!caps_valid(k) || ndocs < 1 || prof == P_NONE) return nullptr;
     mth_store* s = (mth_store*)calloc(1, sizeof(mth_store));
     s->profile = prof;
     s->ndocs = ndocs;
-    int64_t bytes = prof == 0 ? store_layout(s->s0, k, ndocs)
-                  : prof == 1 ? store_layout(s->s1, k, ndocs)
-                  : prof == 3 ? store_layout(s->s3, k, ndocs)
-                  : prof == 4 ? store_layout(s->s4, k, ndocs)
-                              : store_layout(s->s2, k, ndocs);
-    s->mem = host_store_alloc(bytes);
-    if (!s->mem) {
+    int64_t bytes = store_layout(s->st, prof, k, ndocs);
+    s->st.base = host_store_alloc(bytes);
+    if (!s->st.base) {
         free(s);
         return nullptr;
     }
-    s->s0.base = s->s1.base = s->s2.base = s->s3.base = s->s4.base = s->mem;
     for (int64_t d = 0; d < ndocs; d++) with_replica(s, d, [](auto& r) { r.init(); return 0; });
     return s;
 }
@@ -101,7 +72,7 @@ mth_store* mth_create_fx2(int64_t ndocs, const int32_t* caps6, int32_t dcap, int
 void mth_destroy(mth_store* s) {
     if (!s) return;
     free(s->vkind);
-    free(s->mem);
+    free(s->st.base);
     free(s);
 }
 

@@ -814,15 +814,10 @@ struct mt_engine {
     int32_t pcap = 0; /* PermutationVector handles per document (0: none) */
     bool fx = false;  /* delta events or local references: the client-feature replay build */
     bool loads = false; /* the staged batch holds snapshot-load records (the config-2/3 kernel's full build) */
-    int profile = 0;
+    Profile profile = P_SMALL;
     int waves = 8;    /* occupancy target of the HBM-resident small-profile kernel */
     bool wide = false; /* tiled profile: the variant with the heap in HBM and the full window set (promotion target) */
-    Store<HotSmall> s0;
-    Store<HotMid> s1;
-    Store<HotBig> s2;
-    Store<HotMat> s3;
-    Store<HotHuge> s4;
-    void* mem = nullptr;
+    AnyStore st = {};  /* the documents' blocks (st.base: device memory the engine owns) */
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
@@ -930,13 +925,10 @@ const ProfOps* ops_mid();
 const ProfOps* ops_big();
 const ProfOps* ops_huge();
 
+/* the engine's store as the kernels of its profile take it */
 template <class HT>
-static inline Store<HT>& store_of(mt_engine* e) {
-    if constexpr (std::is_same_v<HT, HotSmall>) return e->s0;
-    else if constexpr (std::is_same_v<HT, HotMid>) return e->s1;
-    else if constexpr (std::is_same_v<HT, HotBig>) return e->s2;
-    else if constexpr (std::is_same_v<HT, HotMat>) return e->s3;
-    else return e->s4;
+static inline Store<HT> store_of(const mt_engine* e) {
+    return e->st.as<HT>();
 }
 
 /* one replay kernel over the staged batch (a document per workgroup) */
@@ -958,7 +950,7 @@ static inline int32_t launch_replay(mt_engine* e, K kern, int block = WG) {
 template <class HT>
 struct Launch {
     static int32_t init(mt_engine* e) {
-        Store<HT>& st = store_of<HT>(e);
+        const Store<HT> st = store_of<HT>(e);
         hipLaunchKernelGGL((k_init<HT>), docs_grid(e->ndocs), dim3(WG), 0, e->stream, st, e->ndocs);
         int32_t rc = launch_check(e, "k_init");
         if (rc || !e->collab) return rc;

@@ -20,7 +20,17 @@ static int32_t ensure(mt_engine* e, DevBuf& b, size_t bytes) {
     return MT_OK;
 }
 
-static int32_t launch_init(mt_engine* e) { return e->ops->init(e); }
+/* each profile's launchers (mt_prof_*.hip) */
+static const ProfOps* ops_for(Profile p) {
+    switch (p) {
+    case P_SMALL: return ops_small();
+    case P_MAT: return ops_mat();
+    case P_MID: return ops_mid();
+    case P_BIG: return ops_big();
+    case P_HUGE: return ops_huge();
+    default: return nullptr;
+    }
+}
 
 /* ---- staging the op logs ------------------------------------------------------------------------ */
 struct SubmitArgs {
@@ -229,14 +239,41 @@ static int32_t stage_h2d(mt_engine* e, void* dst, const void* src, size_t n, boo
     return MT_OK;
 }
 
+/* stage a batch (mt_engine_submit: nsub = -1, an entry per document; mt_engine_submit_docs: an entry for each of the
+ * nsub documents listed in `docs`) */
+static int32_t submit(mt_engine* e, const SubmitArgs& a, int64_t nsub, const int64_t* docs) {
+    const int64_t m = nsub < 0 ? e->ndocs : nsub; /* staged entries */
+    if (!offsets_ok(a, m)) return MT_E_ARG;
+    std::vector<mt_engine::Persp> persp((size_t)m);
+    std::vector<char> loads((size_t)m, 0);
+    seed_segk(e, persp, docs);
+    if (!check_range(a, 0, m, persp.data(), loads.data(), nullptr)) return MT_E_ARG;
+    HIPCHK(e, hipSetDevice(e->device));
+    int32_t rc;
+    if ((rc = ensure_staging(e, a, m))) return rc;
+    if (nsub >= 0 && (rc = ensure(e, e->sub, sizeof(int32_t) * (size_t)std::max<int64_t>(m, 1)))) return rc;
+    e->nsub = nsub;
+    e->h_sub.assign(docs, docs + std::max<int64_t>(nsub, 0));
+    const std::vector<int32_t> ids(e->h_sub.begin(), e->h_sub.end());
+    const int64_t nops = a.op_off[m];
+    if (nops) HIPCHK(e, hipMemcpyAsync(e->ops_buf.p, a.ops, sizeof(mt_op_rec) * nops, hipMemcpyHostToDevice, e->stream));
+    if (a.text_units) HIPCHK(e, hipMemcpyAsync(e->text.p, a.text, 2 * a.text_units, hipMemcpyHostToDevice, e->stream));
+    if (!ids.empty())
+        HIPCHK(e, hipMemcpyAsync(e->sub.p, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice, e->stream));
+    if ((rc = copy_small(e, a, e->stream, m))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    keep_staged(e, a, persp, loads);
+    return MT_OK;
+}
+
 extern "C" {
 
 int32_t mt_engine_create(int32_t device, int64_t ndocs, const mt_caps* caps, mt_engine** out) {
     if (!out || !caps || ndocs < 1 || ndocs > (int64_t)0x7fffffff) return MT_E_ARG;
     *out = nullptr;
     Caps k = {caps->acap, caps->mcap, caps->gcap, caps->dcap, caps->rcap, caps->pcap};
-    int prof = profile_for(caps->ncap);
-    if (!caps_valid(k) || prof < 0 || caps->ccap > 254 || caps->dcap < 0 || caps->rcap < 0 || caps->pcap < 0 ||
+    Profile prof = profile_for(caps->ncap);
+    if (!caps_valid(k) || prof == P_NONE || caps->ccap > 254 || caps->dcap < 0 || caps->rcap < 0 || caps->pcap < 0 ||
         caps->pcap > (1 << 24))
         return MT_E_ARG; /* short ids are bytes; 0xFF = LocalClientId */
     mt_engine* e = new mt_engine();
@@ -251,7 +288,7 @@ int32_t mt_engine_create(int32_t device, int64_t ndocs, const mt_caps* caps, mt_
     e->caps0 = *caps;
     e->pro.assign((size_t)ndocs, -1);
     e->profile = prof;
-    e->ops = prof == 0 ? ops_small() : prof == 1 ? ops_mid() : prof == 3 ? ops_mat() : prof == 4 ? ops_huge() : ops_big();
+    e->ops = ops_for(prof);
     if (hipSetDevice(device) != hipSuccess) {
         delete e;
         return MT_E_HIP;
@@ -264,16 +301,11 @@ int32_t mt_engine_create(int32_t device, int64_t ndocs, const mt_caps* caps, mt_
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
     e->waves = ndocs <= (int64_t)ncu * 3 ? 1 : ndocs <= (int64_t)ncu * 4 * 4 ? 4 : 8;
     if (const char* sw = getenv("MT_SMALL_WAVES")) e->waves = atoi(sw) == 1 ? 1 : atoi(sw) == 4 ? 4 : 8;
-    int64_t bytes = prof == 0 ? store_layout(e->s0, k, ndocs)
-                  : prof == 1 ? store_layout(e->s1, k, ndocs)
-                  : prof == 3 ? store_layout(e->s3, k, ndocs)
-                  : prof == 4 ? store_layout(e->s4, k, ndocs)
-                              : store_layout(e->s2, k, ndocs);
-    if (hipMalloc(&e->mem, (size_t)bytes) != hipSuccess) {
+    int64_t bytes = store_layout(e->st, prof, k, ndocs);
+    if (hipMalloc((void**)&e->st.base, (size_t)bytes) != hipSuccess) {
         delete e;
         return MT_E_NOMEM;
     }
-    e->s0.base = e->s1.base = e->s2.base = e->s3.base = e->s4.base = (uint8_t*)e->mem;
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess) {
         mt_engine_destroy(e);
@@ -283,11 +315,11 @@ int32_t mt_engine_create(int32_t device, int64_t ndocs, const mt_caps* caps, mt_
      * stream is not ordered with a non-blocking stream: a large store's fill could still be running
      * when k_init wrote the last documents' headers, and zeroed them after it (round 2: the last
      * documents of a 3.2 GB tiled store failed at their first events, only in long test runs). */
-    if (hipMemsetAsync(e->mem, 0, (size_t)bytes, e->stream) != hipSuccess) {
+    if (hipMemsetAsync(e->st.base, 0, (size_t)bytes, e->stream) != hipSuccess) {
         mt_engine_destroy(e);
         return MT_E_HIP;
     }
-    if (launch_init(e) != MT_OK || hipStreamSynchronize(e->stream) != hipSuccess) {
+    if (e->ops->init(e) != MT_OK || hipStreamSynchronize(e->stream) != hipSuccess) {
         mt_engine_destroy(e);
         return MT_E_HIP;
     }
@@ -305,7 +337,7 @@ void mt_engine_destroy(mt_engine* e) {
                       &e->kv,     &e->kv_off, &e->tmp,  &e->local_ids, &e->prof, &e->order, &e->sub, &e->vkind};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
-    if (e->mem) (void)hipFree(e->mem);
+    if (e->st.base) (void)hipFree(e->st.base);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -370,25 +402,7 @@ int32_t mt_engine_submit(mt_engine* e, const mt_op_rec* ops, const int64_t* op_o
                          int64_t text_units, const int64_t* text_off, const mt_props_rec* props, int64_t nprops,
                          const int64_t* props_off, const mt_kv* kv, int64_t nkv, const int64_t* kv_off) {
     if (!e) return MT_E_ARG;
-    const SubmitArgs a{ops, op_off, text, text_units, text_off, props, nprops, props_off, kv, nkv, kv_off};
-    if (!offsets_ok(a, e->ndocs)) return MT_E_ARG;
-    int64_t nd = e->ndocs;
-    int64_t nops = op_off[nd];
-    std::vector<mt_engine::Persp> persp((size_t)nd);
-    std::vector<char> loads((size_t)nd, 0);
-    seed_segk(e, persp, nullptr);
-    if (!check_range(a, 0, nd, persp.data(), loads.data(), nullptr)) return MT_E_ARG;
-    HIPCHK(e, hipSetDevice(e->device));
-    int32_t rc;
-    if ((rc = ensure_staging(e, a))) return rc;
-    e->nsub = -1;
-    e->h_sub.clear();
-    if (nops) HIPCHK(e, hipMemcpyAsync(e->ops_buf.p, ops, sizeof(mt_op_rec) * nops, hipMemcpyHostToDevice, e->stream));
-    if (text_units) HIPCHK(e, hipMemcpyAsync(e->text.p, text, 2 * text_units, hipMemcpyHostToDevice, e->stream));
-    if ((rc = copy_small(e, a, e->stream))) return rc;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    keep_staged(e, a, persp, loads);
-    return MT_OK;
+    return submit(e, {ops, op_off, text, text_units, text_off, props, nprops, props_off, kv, nkv, kv_off}, -1, nullptr);
 }
 
 int32_t mt_engine_submit_docs(mt_engine* e, int64_t m, const int64_t* docs, const mt_op_rec* ops, const int64_t* op_off,
@@ -398,27 +412,7 @@ int32_t mt_engine_submit_docs(mt_engine* e, int64_t m, const int64_t* docs, cons
     if (!e || m < 0 || m > e->ndocs || (m && !docs)) return MT_E_ARG;
     for (int64_t k = 0; k < m; k++)
         if (docs[k] < 0 || docs[k] >= e->ndocs || (k && docs[k] <= docs[k - 1])) return MT_E_ARG; /* increasing ids */
-    const SubmitArgs a{ops, op_off, text, text_units, text_off, props, nprops, props_off, kv, nkv, kv_off};
-    if (!offsets_ok(a, m)) return MT_E_ARG;
-    std::vector<mt_engine::Persp> persp((size_t)m);
-    std::vector<char> loads((size_t)m, 0);
-    seed_segk(e, persp, docs);
-    if (!check_range(a, 0, m, persp.data(), loads.data(), nullptr)) return MT_E_ARG;
-    HIPCHK(e, hipSetDevice(e->device));
-    int32_t rc;
-    if ((rc = ensure_staging(e, a, m))) return rc;
-    if ((rc = ensure(e, e->sub, sizeof(int32_t) * (size_t)std::max<int64_t>(m, 1)))) return rc;
-    e->h_sub.assign(docs, docs + m);
-    std::vector<int32_t> ids(docs, docs + m);
-    int64_t nops = op_off[m];
-    if (nops) HIPCHK(e, hipMemcpyAsync(e->ops_buf.p, ops, sizeof(mt_op_rec) * nops, hipMemcpyHostToDevice, e->stream));
-    if (text_units) HIPCHK(e, hipMemcpyAsync(e->text.p, text, 2 * text_units, hipMemcpyHostToDevice, e->stream));
-    if (m) HIPCHK(e, hipMemcpyAsync(e->sub.p, ids.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, e->stream));
-    if ((rc = copy_small(e, a, e->stream, m))) return rc;
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->nsub = m;
-    keep_staged(e, a, persp, loads);
-    return MT_OK;
+    return submit(e, {ops, op_off, text, text_units, text_off, props, nprops, props_off, kv, nkv, kv_off}, m, docs);
 }
 
 int32_t mt_host_alloc(int64_t bytes, void** out) {
@@ -440,7 +434,7 @@ int32_t mt_engine_reset(mt_engine* e) {
     std::fill(e->pro.begin(), e->pro.end(), -1);
     e->pro_docs.clear();
     e->fresh = true;
-    return launch_init(e);
+    return e->ops->init(e);
 }
 
 static int32_t stage_subset(mt_engine* e, mt_engine* o);
@@ -466,9 +460,9 @@ static int64_t chunk_docs(const mt_engine* e) {
     if (e->chunk > 0) return e->chunk;
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || ncu < 1) ncu = 256;
-    int64_t resident = e->profile == 4                      ? ncu
-                       : e->profile == 0 && e->waves == 1 ? (int64_t)ncu * 3 /* the LDS-image build */
-                                                          : (int64_t)ncu * 4 * (e->profile == 0 ? e->waves : 7);
+    int64_t resident = e->profile == P_HUGE                       ? ncu
+                       : e->profile == P_SMALL && e->waves == 1 ? (int64_t)ncu * 3 /* the LDS-image build */
+                                                                : (int64_t)ncu * 4 * (e->profile == P_SMALL ? e->waves : 7);
     return std::max<int64_t>(resident, (e->ndocs + 7) / 8);
 }
 
@@ -634,28 +628,21 @@ static int32_t read_hdr(mt_engine* e, int32_t* err, int32_t* err_op, int32_t* st
  * documents' records are gathered on the device; their text / props / kv pools stay the parent's. */
 static int32_t next_ncap(const mt_engine* e) {
     switch (e->profile) {
-    case 0: case 3: return HotMid::N;
-    case 1: return HotBig::N;
-    case 2: return HotHuge::N;
-    case 4: return e->fx || e->wide ? -1 : HotHuge::N; /* the tiled kernel's LDS heap -> its wide variant */
+    case P_SMALL: case P_MAT: return HotMid::N;
+    case P_MID: return HotBig::N;
+    case P_BIG: return HotHuge::N;
+    case P_HUGE: return e->fx || e->wide ? -1 : HotHuge::N; /* the tiled kernel's LDS heap -> its wide variant */
     default: return -1;
     }
 }
-extern "C++" {
-template <class T>
-static void scatter(T* dst, const std::vector<T>& src, const std::vector<int64_t>& docs, int k) {
-    for (size_t i = 0; i < docs.size(); i++)
-        for (int j = 0; j < k; j++) dst[docs[i] * k + j] = src[i * k + j];
-}
-}
-/* stage, in `o`, the records `e` has staged for its promoted documents (e->pro_docs, in order), gathered
- * device to device; their text / props / kv pools stay the parent's */
 /* the staged entry holding document d's records (-1: none staged for it) */
 static int64_t staged_entry(const mt_engine* e, int64_t d) {
     if (e->nsub < 0) return d;
     auto it = std::lower_bound(e->h_sub.begin(), e->h_sub.end(), d);
     return it != e->h_sub.end() && *it == d ? (int64_t)(it - e->h_sub.begin()) : -1;
 }
+/* stage, in `o`, the records `e` has staged for its promoted documents (e->pro_docs, in order), gathered
+ * device to device; their text / props / kv pools stay the parent's */
 static int32_t stage_subset(mt_engine* e, mt_engine* o) {
     int64_t m = (int64_t)e->pro_docs.size();
     int32_t rc;
@@ -732,7 +719,7 @@ static int32_t promote(mt_engine* e) {
         e->over = o;
     }
     o->promote = e->promote;
-    o->wide = e->profile == 4; /* HotHuge -> HotHuge: the same layout, the wide kernel */
+    o->wide = e->profile == P_HUGE; /* HotHuge -> HotHuge: the same layout, the wide kernel */
     if (e->nvk && (rc = mt_engine_set_value_kinds(o, e->h_vkind.data(), e->nvk))) return rc;
     if (e->collab) {
         std::vector<int32_t> loc((size_t)(3 * m)); /* the promoted documents' ids, minSeqs, currentSeqs */
@@ -769,34 +756,62 @@ static mt_engine* route(mt_engine* e, int64_t* doc) {
 }
 static bool promoted(const mt_engine* e) { return e->over && !e->pro_docs.empty(); }
 
+/* The second half of every whole-batch read. `out` holds `row` entries per document, just read from e's own store;
+ * the rows of e's promoted documents are read again from `over` (read_child(over, tmp): its rows are `crow` entries
+ * long, and the call goes on through over's own promotions) and put back over them. A row keeps the first
+ * min(row, crow) entries of its child row. out == nullptr (an output the caller did not ask for): the child is read
+ * with nullptr. A read with two outputs nests two calls, so that one read of the child fills both temporaries. */
+extern "C++" {
+template <class T, class F>
+static int32_t read_promoted(mt_engine* e, T* out, size_t row, size_t crow, F&& read_child) {
+    if (!promoted(e)) return MT_OK;
+    const size_t m = e->pro_docs.size();
+    std::vector<T> tmp(out ? m * crow : 0);
+    int32_t rc = read_child(e->over, out ? tmp.data() : nullptr);
+    if (rc || !out) return rc;
+    for (size_t i = 0; i < m; i++)
+        std::copy_n(tmp.data() + i * crow, std::min(row, crow), out + (size_t)e->pro_docs[i] * row);
+    return MT_OK;
+}
+
+/* The second half of every variable-length read of one document: fetch what the device holds at `dhdr`, wait, take
+ * the count n = count(header), copy min(n, cap) elements of `unit` bytes from `dsrc` to `out` (`whole`: all n, or
+ * none if they do not fit), wait. out == nullptr: the size query. Returns n, or the negated MT_E_* code. */
+template <class H, class N>
+static int64_t read_counted(mt_engine* e, const H* dhdr, N&& count, const void* dsrc, size_t unit, void* out,
+                            int64_t cap, bool whole = false) {
+    H hdr;
+    if (hipMemcpyAsync(&hdr, dhdr, sizeof hdr, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    const int64_t n = count(hdr);
+    const int64_t m = n <= cap ? n : whole ? 0 : cap;
+    if (out && m > 0) {
+        if (hipMemcpyAsync(out, dsrc, unit * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+            return -MT_E_HIP;
+        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    }
+    return n;
+}
+}
+static int64_t whole_count(int64_t n) { return n; } /* read_counted's `count` where the device wrote the count itself */
+
 int32_t mt_engine_errors(mt_engine* e, int32_t* err, int32_t* err_op) {
     if (!e) return MT_E_ARG;
     int32_t rc = read_hdr(e, err, err_op, nullptr, nullptr);
-    if (rc || !promoted(e)) return rc;
-    size_t m = e->pro_docs.size();
-    std::vector<int32_t> a(m), b(m);
-    if ((rc = mt_engine_errors(e->over, a.data(), b.data()))) return rc;
-    if (err) scatter(err, a, e->pro_docs, 1);
-    if (err_op) scatter(err_op, b, e->pro_docs, 1);
-    return MT_OK;
+    if (rc) return rc;
+    return read_promoted(e, err, 1, 1, [&](mt_engine* o, int32_t* a) {
+        return read_promoted(e, err_op, 1, 1, [&](mt_engine*, int32_t* b) { return mt_engine_errors(o, a, b); });
+    });
 }
 int32_t mt_engine_stats(mt_engine* e, int32_t* out4) {
     if (!e || !out4) return MT_E_ARG;
     int32_t rc = read_hdr(e, nullptr, nullptr, out4, nullptr);
-    if (rc || !promoted(e)) return rc;
-    std::vector<int32_t> a(4 * e->pro_docs.size());
-    if ((rc = mt_engine_stats(e->over, a.data()))) return rc;
-    scatter(out4, a, e->pro_docs, 4);
-    return MT_OK;
+    return rc ? rc : read_promoted(e, out4, 4, 4, mt_engine_stats);
 }
 int32_t mt_engine_doc_times(mt_engine* e, int64_t* out2) {
     if (!e || !out2) return MT_E_ARG;
     int32_t rc = read_hdr(e, nullptr, nullptr, nullptr, nullptr, out2);
-    if (rc || !promoted(e)) return rc;
-    std::vector<int64_t> a(2 * e->pro_docs.size());
-    if ((rc = mt_engine_doc_times(e->over, a.data()))) return rc;
-    scatter(out2, a, e->pro_docs, 2);
-    return MT_OK;
+    return rc ? rc : read_promoted(e, out2, 2, 2, mt_engine_doc_times);
 }
 
 int32_t mt_engine_set_order(mt_engine* e, const int32_t* order) {
@@ -854,11 +869,7 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
 int32_t mt_engine_work(mt_engine* e, int64_t* out3) {
     if (!e || !out3) return MT_E_ARG;
     int32_t rc = read_hdr(e, nullptr, nullptr, nullptr, out3);
-    if (rc || !promoted(e)) return rc;
-    std::vector<int64_t> a(3 * e->pro_docs.size());
-    if ((rc = mt_engine_work(e->over, a.data()))) return rc;
-    scatter(out3, a, e->pro_docs, 3);
-    return MT_OK;
+    return rc ? rc : read_promoted(e, out3, 3, 3, mt_engine_work);
 }
 int64_t mt_engine_promoted(const mt_engine* e, int64_t* docs_out, int64_t cap) {
     if (!e) return -MT_E_ARG;
@@ -876,12 +887,7 @@ int32_t mt_engine_digests(mt_engine* e, uint64_t* out) {
     if (rc) return rc;
     HIPCHK(e, hipMemcpyAsync(out, e->tmp.p, sizeof(uint64_t) * e->ndocs, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (promoted(e)) {
-        std::vector<uint64_t> a(e->pro_docs.size());
-        if ((rc = mt_engine_digests(e->over, a.data()))) return rc;
-        scatter(out, a, e->pro_docs, 1);
-    }
-    return MT_OK;
+    return read_promoted(e, out, 1, 1, mt_engine_digests);
 }
 
 int64_t mt_engine_dump(mt_engine* e, int64_t doc, uint8_t* out, int64_t cap) {
@@ -894,14 +900,7 @@ int64_t mt_engine_dump(mt_engine* e, int64_t doc, uint8_t* out, int64_t cap) {
     uint8_t* dbuf = out ? (uint8_t*)e->tmp.p + 16 : nullptr;
     int32_t rc = e->ops->dump(e, doc, dbuf, out ? cap : 0, dn);
     if (rc) return -rc;
-    int64_t n = 0;
-    if (hipMemcpyAsync(&n, dn, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    if (out && n <= cap) {
-        if (hipMemcpyAsync(out, dbuf, n, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    }
-    return n;
+    return read_counted(e, dn, whole_count, dbuf, 1, out, cap, true); /* all n bytes or none */
 }
 
 int32_t mt_engine_get_length(mt_engine* e, int64_t doc, int32_t ref_seq, int32_t long_client, int32_t* out) {
@@ -961,15 +960,7 @@ static int64_t text_read(mt_engine* e, int64_t doc, int32_t ref_seq, int32_t lon
     int32_t rc = e->ops->text(e, doc, ref_seq, long_client, floor, start, end, dph, placeholder_len, dbuf,
                               out ? cap : 0, dn);
     if (rc) return -rc;
-    int64_t n = 0;
-    if (hipMemcpyAsync(&n, dn, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    if (out) {
-        int64_t m = n < cap ? n : cap;
-        if (m > 0 && hipMemcpyAsync(out, dbuf, 2 * m, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    }
-    return n;
+    return read_counted(e, dn, whole_count, dbuf, 2, out, cap);
 }
 
 static void seg_ref_of(const int32_t* r, mt_seg_ref* out) {
@@ -1088,51 +1079,39 @@ int64_t mt_engine_segment_ids(mt_engine* e, int64_t doc, int32_t* out, int64_t c
     int32_t* dbuf = (int32_t*)((uint8_t*)e->tmp.p + 16);
     int32_t rc = e->ops->segids(e, doc, dbuf, out ? cap : 0, dn);
     if (rc) return -rc;
-    int64_t n = 0;
-    if (hipMemcpyAsync(&n, dn, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    int64_t m = n < cap ? n : cap;
-    if (out && m > 0) {
-        if (hipMemcpyAsync(out, dbuf, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    }
-    return n;
+    return read_counted(e, dn, whole_count, dbuf, 8, out, cap);
 }
 
-/* the delta region of every document: offset inside a document's block, and the block stride */
-static void delta_geometry(const mt_engine* e, int64_t* off, int64_t* stride) {
-    switch (e->profile) {
-    case 0: *off = Doc<HotSmall>::off_dl(e->s0.caps), *stride = e->s0.stride; break;
-    case 1: *off = Doc<HotMid>::off_dl(e->s1.caps), *stride = e->s1.stride; break;
-    case 3: *off = Doc<HotMat>::off_dl(e->s3.caps), *stride = e->s3.stride; break;
-    case 4: *off = Doc<HotHuge>::off_dl(e->s4.caps), *stride = e->s4.stride; break;
-    default: *off = Doc<HotBig>::off_dl(e->s2.caps), *stride = e->s2.stride; break;
-    }
+/* where the host reads a document's block directly: the block (its header is at the start), the DState at the head
+ * of its delta region (the logged words follow it) and its handle table */
+struct DocBlock {
+    const uint8_t* hdr;
+    const DState* dstate;
+    const int32_t* ht;
+};
+static DocBlock doc_block(const mt_engine* e, int64_t doc) {
+    return with_profile(e->profile, [&](auto tag) {
+        typedef Doc<typename decltype(tag)::Hot> D;
+        const uint8_t* b = e->st.base + doc * e->st.stride;
+        return DocBlock{b, (const DState*)(b + D::off_dl(e->st.caps)), (const int32_t*)(b + D::off_ht(e->st.caps))};
+    });
 }
 
 int32_t mt_engine_delta_state(mt_engine* e, int64_t* n_out, uint64_t* hash_out) {
     if (!e || e->dcap <= 0) return MT_E_ARG;
     HIPCHK(e, hipSetDevice(e->device));
-    int64_t off, stride;
-    delta_geometry(e, &off, &stride);
     std::vector<DState> st((size_t)e->ndocs);
     /* one strided copy: the DState at the head of each document's delta region */
-    HIPCHK(e, hipMemcpy2DAsync(st.data(), sizeof(DState), (const uint8_t*)e->mem + off, (size_t)stride, sizeof(DState),
+    HIPCHK(e, hipMemcpy2DAsync(st.data(), sizeof(DState), doc_block(e, 0).dstate, (size_t)e->st.stride, sizeof(DState),
                                (size_t)e->ndocs, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     for (int64_t d = 0; d < e->ndocs; d++) {
         if (n_out) n_out[d] = st[d].n;
         if (hash_out) hash_out[d] = st[d].h;
     }
-    if (promoted(e)) {
-        std::vector<int64_t> a(e->pro_docs.size());
-        std::vector<uint64_t> b(e->pro_docs.size());
-        int32_t rc = mt_engine_delta_state(e->over, a.data(), b.data());
-        if (rc) return rc;
-        if (n_out) scatter(n_out, a, e->pro_docs, 1);
-        if (hash_out) scatter(hash_out, b, e->pro_docs, 1);
-    }
-    return MT_OK;
+    return read_promoted(e, n_out, 1, 1, [&](mt_engine* o, int64_t* a) {
+        return read_promoted(e, hash_out, 1, 1, [&](mt_engine*, uint64_t* b) { return mt_engine_delta_state(o, a, b); });
+    });
 }
 
 int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
@@ -1140,30 +1119,16 @@ int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
     const int64_t dcap = e->dcap; /* the caller's engine's: a promoted document's engine logs four times as many */
     e = route(e, &doc);
     if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
-    int64_t off, stride;
-    delta_geometry(e, &off, &stride);
-    const uint8_t* base = (const uint8_t*)e->mem + doc * stride + off;
-    DState st;
-    if (hipMemcpyAsync(&st, base, sizeof st, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    int64_t logged = st.n < dcap ? st.n : dcap;
-    int64_t m = logged < cap ? logged : cap;
-    if (out && m > 0) {
-        if (hipMemcpyAsync(out, base + sizeof(DState), 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
-            return -MT_E_HIP;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    }
-    return logged;
+    const DState* ds = doc_block(e, doc).dstate;
+    return read_counted(e, ds, [&](const DState& st) { return std::min(st.n, dcap); }, ds + 1, 4, out, cap);
 }
 
 int32_t mt_engine_doc_error(mt_engine* e, int64_t doc, int32_t* err, int32_t* err_op) {
     if (!e || doc < 0 || doc >= e->ndocs) return MT_E_ARG;
     e = route(e, &doc);
     HIPCHK(e, hipSetDevice(e->device));
-    int64_t stride = 0, off = 0;
-    delta_geometry(e, &off, &stride); /* the block stride; the header is at the block's start */
     int32_t v[2];
-    const uint8_t* h = (const uint8_t*)e->mem + doc * stride + offsetof(DocHdr, err);
+    const uint8_t* h = doc_block(e, doc).hdr + offsetof(DocHdr, err);
     static_assert(offsetof(DocHdr, errOp) == offsetof(DocHdr, err) + 4, "err, errOp adjacent");
     HIPCHK(e, hipMemcpyAsync(v, h, sizeof v, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1174,34 +1139,12 @@ int32_t mt_engine_doc_error(mt_engine* e, int64_t doc, int32_t* err, int32_t* er
 
 int32_t mt_engine_ref_capacity(const mt_engine* e) { return e ? e->rcap : 0; }
 
-static void ht_geometry(const mt_engine* e, int64_t* off, int64_t* dl) {
-    switch (e->profile) {
-    case 0: *off = Doc<HotSmall>::off_ht(e->s0.caps), *dl = Doc<HotSmall>::off_dl(e->s0.caps); break;
-    case 1: *off = Doc<HotMid>::off_ht(e->s1.caps), *dl = Doc<HotMid>::off_dl(e->s1.caps); break;
-    case 3: *off = Doc<HotMat>::off_ht(e->s3.caps), *dl = Doc<HotMat>::off_dl(e->s3.caps); break;
-    case 4: *off = Doc<HotHuge>::off_ht(e->s4.caps), *dl = Doc<HotHuge>::off_dl(e->s4.caps); break;
-    default: *off = Doc<HotBig>::off_ht(e->s2.caps), *dl = Doc<HotBig>::off_dl(e->s2.caps); break;
-    }
-}
-
 int64_t mt_engine_handle_table(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
     if (!e || e->pcap <= 0 || doc < 0 || doc >= e->ndocs || cap < 0) return -MT_E_ARG;
     e = route(e, &doc);
     if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
-    int64_t off, dl, stride, o2;
-    ht_geometry(e, &off, &dl);
-    delta_geometry(e, &o2, &stride);
-    const uint8_t* base = (const uint8_t*)e->mem + doc * stride;
-    DState st;
-    if (hipMemcpyAsync(&st, base + dl, sizeof st, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    int64_t n = st.hlen, m = n < cap ? n : cap;
-    if (out && m > 0) {
-        if (hipMemcpyAsync(out, base + off, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
-            return -MT_E_HIP;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
-    }
-    return n;
+    const DocBlock b = doc_block(e, doc);
+    return read_counted(e, b.dstate, [](const DState& st) { return (int64_t)st.hlen; }, b.ht, 4, out, cap);
 }
 
 int32_t mt_engine_get_handle(mt_engine* e, int64_t doc, int32_t pos, int32_t* out) {
@@ -1228,19 +1171,13 @@ int32_t mt_engine_ref_positions(mt_engine* e, int32_t* nref_out, int32_t* pos_ou
     if (pos_out)
         HIPCHK(e, hipMemcpyAsync(pos_out, dpos, 4 * (size_t)n * e->rcap, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (promoted(e)) {
-        size_t m = e->pro_docs.size();
-        /* the promoted engine's rows have its own (larger) length; the caller's rows keep e->rcap entries, the
-         * first of each child row. nref stays the true count (it may exceed e->rcap). */
-        size_t crow = (size_t)mt_engine_ref_capacity(e->over), row = (size_t)e->rcap;
-        std::vector<int32_t> a(m), b(m * crow);
-        if ((rc = mt_engine_ref_positions(e->over, a.data(), pos_out ? b.data() : nullptr))) return rc;
-        if (nref_out) scatter(nref_out, a, e->pro_docs, 1);
-        if (pos_out)
-            for (size_t i = 0; i < m; i++)
-                std::copy_n(b.data() + i * crow, std::min(row, crow), pos_out + (size_t)e->pro_docs[i] * row);
-    }
-    return MT_OK;
+    /* the promoted engine's rows have its own (larger) length; the caller's rows keep e->rcap entries, the first of
+     * each child row. nref stays the true count (it may exceed e->rcap). */
+    const size_t crow = promoted(e) ? (size_t)e->over->rcap : 0;
+    return read_promoted(e, nref_out, 1, 1, [&](mt_engine* o, int32_t* a) {
+        return read_promoted(e, pos_out, (size_t)e->rcap, crow,
+                             [&](mt_engine*, int32_t* b) { return mt_engine_ref_positions(o, a, b); });
+    });
 }
 
 #ifdef MT_PROF

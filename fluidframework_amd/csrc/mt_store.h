@@ -52,14 +52,52 @@ inline int64_t store_layout(Store<HT>& st, const Caps& caps, int64_t ndocs) {
 
 inline bool caps_valid(const Caps& k) { return k.acap >= 16 && k.mcap >= 4 && k.gcap >= 1; }
 
-/* profiles: 0 = HotSmall, 3 = HotMat, 1 = HotMid, 2 = HotBig, 4 = HotHuge (tiled, config 4) */
-inline int profile_for(int32_t ncap) {
-    if (ncap <= HotSmall::N) return 0;
-    if (ncap <= HotMat::N) return 3;
-    if (ncap <= HotMid::N) return 1;
-    if (ncap <= HotBig::N) return 2;
-    if (ncap <= HotHuge::N) return 4;
-    return -1;
+/* profiles: the hot image type a store's documents use (P_HUGE: tiled, config 4) */
+enum Profile : int { P_NONE = -1, P_SMALL = 0, P_MID = 1, P_BIG = 2, P_MAT = 3, P_HUGE = 4 };
+
+inline Profile profile_for(int32_t ncap) {
+    if (ncap <= HotSmall::N) return P_SMALL;
+    if (ncap <= HotMat::N) return P_MAT;
+    if (ncap <= HotMid::N) return P_MID;
+    if (ncap <= HotBig::N) return P_BIG;
+    if (ncap <= HotHuge::N) return P_HUGE;
+    return P_NONE;
+}
+
+/* f(ProfTag<HT>()) for the profile's hot image type HT: the one place a profile number becomes a type.
+ * A generic f names it with `typename decltype(tag)::Hot`. */
+template <class HT>
+struct ProfTag {
+    typedef HT Hot;
+};
+template <class F>
+inline auto with_profile(int prof, F&& f) {
+    switch (prof) {
+    case P_SMALL: return f(ProfTag<HotSmall>());
+    case P_MAT: return f(ProfTag<HotMat>());
+    case P_MID: return f(ProfTag<HotMid>());
+    case P_HUGE: return f(ProfTag<HotHuge>());
+    default: return f(ProfTag<HotBig>());
+    }
+}
+
+/* A store whose profile is known at run time only (what an engine holds): Store<HT> without the type. */
+struct AnyStore {
+    uint8_t* base;
+    int64_t stride;
+    Caps caps;
+
+    template <class HT>
+    Store<HT> as() const {
+        return Store<HT>{base, stride, caps};
+    }
+};
+
+inline int64_t store_layout(AnyStore& st, int prof, const Caps& caps, int64_t ndocs) {
+    st.stride = with_profile(prof, [&](auto tag) { return Doc<typename decltype(tag)::Hot>::stride(caps); });
+    st.caps = caps;
+    st.base = nullptr;
+    return st.stride * ndocs;
 }
 
 } /* namespace mt */

@@ -327,6 +327,16 @@ def test_gpu_reads_of_promoted_documents(trio, text_mix, text_refs, text_oracle,
     err, err_op = a.errors()
     stats = [e.stats() for e in trio]
     work = [e.work() for e in trio]
+    # mt_engine_doc_times: a promoted document reports its replay in the engine that holds it. The C ABI hands out no
+    # promoted engine to read directly, so what pins the values to it is the launch order on the device's one clock:
+    # mt_engine_sync waits for a replay before it promotes, so the second engine's replay starts after every
+    # document's in the first has ended, and the third engine's (the chain document) after the second's.
+    tt = a.doc_times()
+    assert (tt[:, 1] >= tt[:, 0]).all() and (tt[:, 0] > 0).all(), tt
+    up = sorted(pm.TEXT_PROMOTED)
+    stay = [d for d in range(text_refs.ndocs) if d not in pm.TEXT_PROMOTED]
+    assert tt[up, 0].min() >= tt[stay, 1].max(), tt
+    assert tt[pm.TEXT_CHAIN, 0] >= tt[[d for d in up if d != pm.TEXT_CHAIN], 1].max(), tt
     answered = refused = 0
     for d in sorted(pm.TEXT_PROMOTED) + [0, 7]:
         b = _b_for(trio, d)
