@@ -6030,9 +6030,44 @@ struct Replica {
         *a = x < y ? x : y, *b = x < y ? y : x;
     }
     static constexpr int64_t PH_RUN_MAX = 1 << 24;
+    /* The wave writes dst[0, lim): the concatenation of the lanes' pieces, lane l's starting at unit eo (the
+     * exclusive scan of the piece lengths, so non-decreasing over the lanes; lim <= their total). A text piece
+     * is base[src ..], a placeholder piece (src < 0) repeats ph[0, pl). The lanes stride over the run two units
+     * at a time, the pairs aligned to 4 bytes in dst (one dword store per lane; a pair half outside [0, lim), as
+     * at an odd start, is a 2-byte store), and each unit finds its piece by a 6-step search over the lanes'
+     * offsets: the last lane with eo <= u, whose piece is never empty, since eo of the next lane is above u.
+     * Wave-uniform control flow: every lane must call this, with the same dst and lim. */
+    MT_HD void packed_copy(uint16_t* dst, int32_t lim, int32_t eo, int32_t src, const uint16_t* base,
+                           const uint16_t* ph, int32_t pl) {
+        const int32_t par = (int32_t)(((uintptr_t)dst >> 1) & 1); /* dst - par is 4-byte aligned */
+        for (int32_t b = -par; b < lim; b += 2 * W::N) {
+            const int32_t u0 = b + 2 * w.lane();
+            uint32_t x[2];
+            for (int32_t q = 0; q < 2; q++) {
+                const int32_t u = u0 + q;
+                int32_t L = 0, e = w.shfl(eo, 0);
+                for (int32_t st = W::N >> 1; st > 0; st >>= 1) {
+                    int32_t c = w.shfl(eo, L + st);
+                    if (c <= u) L += st, e = c;
+                }
+                const int32_t sb = w.shfl(src, L);
+                x[q] = 0;
+                if (u >= 0 && u < lim) x[q] = sb >= 0 ? base[sb + (u - e)] : ph[(u - e) % pl];
+            }
+            if (u0 >= 0 && u0 + 1 < lim)
+                *(uint32_t*)(dst + u0) = x[0] | (x[1] << 16);
+            else if (u0 >= 0 && u0 < lim)
+                dst[u0] = (uint16_t)x[0];
+            else if (u0 + 1 >= 0 && u0 + 1 < lim)
+                dst[u0 + 1] = (uint16_t)x[1];
+        }
+    }
     MT_HD int64_t get_text(int32_t refSeq, int32_t client, uint16_t* out, int64_t cap) {
         return get_text_range(refSeq, client, 0, INT32_MAX, nullptr, 0, out, cap);
     }
+    /* PACKED (the batched read, mt_kernels.h k_texts): the wave copies a pass's output as one contiguous run
+     * (packed_copy) instead of each lane copying its own piece; the same units either way. */
+    template <bool PACKED = false>
     MT_HD int64_t get_text_range(int32_t refSeq, int32_t client, int32_t start, int32_t end, const uint16_t* ph,
                                  int32_t pl, uint16_t* out, int64_t cap) {
         if (start == TEXT_RANGE_DEFAULT) start = 0;
@@ -6073,7 +6108,12 @@ struct Replica {
                 int32_t ol = !hit ? 0 : text ? b - a : pl * v;
                 int32_t tot;
                 int64_t o = n + w.excl_scan(ol, &tot);
-                if (out && ol > 0 && o < cap) {
+                if constexpr (PACKED) {
+                    /* wave-uniform: every lane takes part in the shuffles */
+                    if (out && tot > 0 && n < cap)
+                        packed_copy(out + n, (int32_t)(tot < cap - n ? tot : cap - n), (int32_t)(o - n),
+                                    hit && text ? (int32_t)cold(s).toff + a : -1, base, ph, pl);
+                } else if (out && ol > 0 && o < cap) {
                     int64_t m = ol < cap - o ? ol : cap - o;
                     if (text) {
                         const uint16_t* src = base + cold(s).toff + a;

@@ -636,15 +636,14 @@ __device__ inline void seg_fields(R& r, int32_t s, int32_t off, int32_t* res) {
     res[9] = r.ordinal_of(s);
 }
 #define MT_SEGQ_N 10
+/* one query of the list above on a replica: res[0..MT_SEGQ_N) (k_seg: one document; k_segs: one per wave) */
 template <class HT>
-__global__ __launch_bounds__(WG) void k_seg(Store<HT> st, int64_t doc, int32_t mode, int32_t a, int32_t b,
-                                           int32_t ref_seq, int32_t long_client, int32_t floor, int32_t* out) {
-    Replica<WaveGPU, HT> r(st.doc(doc), WaveGPU());
-    int32_t res[MT_SEGQ_N] = {0, -1, 0, 0, 0, 0, 0, 0, 0, 0};
+__device__ inline void seg_eval(Replica<WaveGPU, HT>& r, int32_t mode, int32_t a, int32_t b, int32_t ref_seq,
+                                int32_t long_client, int32_t floor, int32_t* res) {
+    res[0] = 0, res[1] = -1;
+    for (int i = 2; i < MT_SEGQ_N; i++) res[i] = 0;
     if (persp_refused(r, ref_seq, long_client, floor)) { /* res[0] = 3: refused (MT_E_UNSUPPORTED) */
         res[0] = 3;
-        if (threadIdx.x == 0)
-            for (int i = 0; i < MT_SEGQ_N; i++) out[i] = res[i];
         return;
     }
     int32_t sh;
@@ -718,8 +717,101 @@ __global__ __launch_bounds__(WG) void k_seg(Store<HT> st, int64_t doc, int32_t m
             res[1] = r.position_of(s, ref_seq, sh);
         }
     }
+}
+template <class HT>
+__global__ __launch_bounds__(WG) void k_seg(Store<HT> st, int64_t doc, int32_t mode, int32_t a, int32_t b,
+                                           int32_t ref_seq, int32_t long_client, int32_t floor, int32_t* out) {
+    Replica<WaveGPU, HT> r(st.doc(doc), WaveGPU());
+    int32_t res[MT_SEGQ_N];
+    seg_eval<HT>(r, mode, a, b, ref_seq, long_client, floor, res);
     if (threadIdx.x == 0)
         for (int i = 0; i < MT_SEGQ_N; i++) out[i] = res[i];
+}
+
+/* ---- batched reads: one wave per query (mt_engine_get_lengths / _texts / _containing_segments / ..._positions) ----
+ * A query names a document of this store, a perspective (ref_seq, long_client < 0 = the local view) with its floor
+ * (persp_refused, filled by the host on the engine the caller holds, before routing), two arguments (a position,
+ * or a text range) and `slot`, the caller's query index: every result lands there, so the queries of one call
+ * can be split over the engines that hold their documents. The reads write nothing into a flat profile's
+ * document block, so a document may be named by several queries of a launch; the tiled profile's position index
+ * keeps scratch in the block (Replica: sdel, swcp, ...), so the host launches its queries of one document one
+ * after the other (mt_replay.hip read_plan). */
+#ifndef MT_TEXTS_PACKED_DEFAULT
+#define MT_TEXTS_PACKED_DEFAULT true /* k_texts' copy: Replica::packed_copy or each lane its own piece */
+#endif
+struct ReadQ {
+    int64_t doc;
+    int32_t ref_seq, long_client, floor;
+    int32_t a, b;
+    int32_t slot;
+};
+/* the perspective set-up of k_text / k_seg */
+template <class R>
+__device__ inline int32_t persp_short(R& r, int32_t* ref_seq, int32_t long_client) {
+    if (long_client < 0) {
+        *ref_seq = r.h.currentSeq;
+        return r.h.localShort;
+    }
+    int32_t sh = r.short_of(long_client);
+    return sh < 0 ? 0x7fff : sh;
+}
+template <class HT>
+__global__ __launch_bounds__(WG) void k_lengths(Store<HT> st, int64_t m, const ReadQ* qs, int32_t* len,
+                                               int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int32_t v = 0, rc = MT_OK;
+    if (persp_refused(r, q.ref_seq, q.long_client, q.floor)) {
+        rc = MT_E_UNSUPPORTED;
+    } else if (q.long_client < 0) {
+        v = r.length_local();
+    } else {
+        int32_t sh = r.short_of(q.long_client);
+        v = r.length(q.ref_seq, sh < 0 ? 0x7fff : sh);
+    }
+    if (threadIdx.x == 0) len[q.slot] = v, status[q.slot] = rc;
+}
+/* the size of query i's text (size[slot]; 0 and status[slot] = MT_E_UNSUPPORTED for a refused one) */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_text_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int32_t pl,
+                                                  int64_t* size, int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int64_t n = -E_UNSUPPORTED;
+    if (!persp_refused(r, q.ref_seq, q.long_client, q.floor)) {
+        int32_t ref_seq = q.ref_seq;
+        int32_t sh = persp_short(r, &ref_seq, q.long_client);
+        n = r.get_text_range(ref_seq, sh, q.a, q.b, nullptr, pl, nullptr, 0);
+    }
+    if (threadIdx.x == 0) size[q.slot] = n < 0 ? 0 : n, status[q.slot] = n < 0 ? (int32_t)-n : MT_OK;
+}
+/* query i's text into out[off[slot], off[slot + 1]) (the host's prefix sum of k_text_sizes' sizes: a failed
+ * query's window is empty); nothing is written outside the window */
+template <class HT, bool PACKED>
+__global__ __launch_bounds__(WG) void k_texts(Store<HT> st, int64_t m, const ReadQ* qs, const uint16_t* ph,
+                                             int32_t pl, const int64_t* off, uint16_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    if (persp_refused(r, q.ref_seq, q.long_client, q.floor)) return;
+    int32_t ref_seq = q.ref_seq;
+    int32_t sh = persp_short(r, &ref_seq, q.long_client);
+    (void)r.template get_text_range<PACKED>(ref_seq, sh, q.a, q.b, ph, pl, out + o, cap);
+}
+/* k_seg's modes 0 and 4 per query (a = the position): res[slot * MT_SEGQ_N ..] */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_segs(Store<HT> st, int64_t m, const ReadQ* qs, int32_t mode, int32_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int32_t res[MT_SEGQ_N];
+    seg_eval<HT>(r, mode, q.a, 0, q.ref_seq, q.long_client, q.floor, res);
+    if (threadIdx.x == 0)
+        for (int i = 0; i < MT_SEGQ_N; i++) out[(int64_t)q.slot * MT_SEGQ_N + i] = res[i];
 }
 
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
@@ -868,6 +960,8 @@ struct mt_engine {
     DevBuf vkind;
     int32_t nvk = 0;
     std::vector<uint8_t> h_vkind;
+    bool texts_packed = MT_TEXTS_PACKED_DEFAULT; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
+    DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
      * sources (each with the event of the last copy out of it) */
@@ -917,6 +1011,13 @@ struct ProfOps {
                    int32_t long_client, int32_t floor, int32_t* dout);
     int32_t (*refpos)(mt_engine* e, int32_t* dn, int32_t* dpos);
     int32_t (*segids)(mt_engine* e, int64_t doc, int32_t* dout, int64_t cap, int64_t* dn);
+    /* the batched reads: dq[0, m) queries of this engine's documents, launched on s (results by ReadQ.slot) */
+    int32_t (*lengths)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t* dlen, int32_t* dstatus);
+    int32_t (*text_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t pl, int64_t* dsize,
+                          int32_t* dstatus);
+    int32_t (*texts)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const uint16_t* dph, int32_t pl,
+                     const int64_t* doff, uint16_t* dout, bool packed);
+    int32_t (*segs)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, int32_t* dres);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1004,7 +1105,33 @@ struct Launch {
         hipLaunchKernelGGL((k_segids<HT>), dim3(1), dim3(WG), 0, e->stream, store_of<HT>(e), doc, dout, cap, dn);
         return launch_check(e, "k_segids");
     }
+    static int32_t lengths(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t* dlen,
+                           int32_t* dstatus) {
+        hipLaunchKernelGGL((k_lengths<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dlen, dstatus);
+        return launch_check(e, "k_lengths");
+    }
+    static int32_t text_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t pl, int64_t* dsize,
+                              int32_t* dstatus) {
+        hipLaunchKernelGGL((k_text_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, pl, dsize,
+                           dstatus);
+        return launch_check(e, "k_text_sizes");
+    }
+    static int32_t texts(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const uint16_t* dph, int32_t pl,
+                         const int64_t* doff, uint16_t* dout, bool packed) {
+        if (packed)
+            hipLaunchKernelGGL((k_texts<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dph, pl,
+                               doff, dout);
+        else
+            hipLaunchKernelGGL((k_texts<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dph, pl,
+                               doff, dout);
+        return launch_check(e, "k_texts");
+    }
+    static int32_t segs(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, int32_t* dres) {
+        hipLaunchKernelGGL((k_segs<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, mode, dres);
+        return launch_check(e, "k_segs");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
-        return ProfOps{init, start_collab, replay, hdr, digest, dump, length, text, seg, refpos, segids};
+        return ProfOps{init, start_collab, replay, hdr,    digest,  dump,       length, text,
+                       seg,  refpos,       segids, lengths, text_sizes, texts,  segs};
     }
 };

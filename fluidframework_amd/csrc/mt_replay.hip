@@ -334,7 +334,8 @@ void mt_engine_destroy(mt_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->borrowed) e->text.p = e->props.p = e->kv.p = nullptr; /* the parent's */
     DevBuf* bufs[] = {&e->ops_buf, &e->op_off, &e->text, &e->text_off, &e->props,     &e->props_off,
-                      &e->kv,     &e->kv_off, &e->tmp,  &e->local_ids, &e->prof, &e->order, &e->sub, &e->vkind};
+                      &e->kv,     &e->kv_off, &e->tmp,  &e->local_ids, &e->prof, &e->order, &e->sub, &e->vkind,
+                      &e->rq};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (e->st.base) (void)hipFree(e->st.base);
@@ -861,6 +862,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value < 0) return MT_E_ARG;
         e->chunk = value;
         return MT_OK;
+    case MT_VAR_TEXTS_PACKED:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->texts_packed = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1029,13 +1034,21 @@ int32_t mt_engine_pos_from_relative_pos(mt_engine* e, int64_t doc, int32_t id_ke
     return MT_OK;
 }
 
+/* what k_seg's mode 4 found for `pos` (r: its MT_SEGQ_N words), as resolveRemoteClientPosition (the segment's local
+ * position + offset, the local length when pos is the remote client's length, else -1) or as adjustPosition (a
+ * segment that exists and is not removed, else -1) */
+static int32_t remote_pos(const int32_t* r, int32_t pos, bool adjust) {
+    if (adjust) return r[0] == 1 && !r[2] ? r[1] : -1;
+    return r[0] == 1 ? r[1] : (pos == r[3] ? r[4] : -1);
+}
+
 int32_t mt_engine_resolve_remote_client_position(mt_engine* e, int64_t doc, int32_t pos, int32_t ref_seq,
                                                  int32_t long_client, int32_t* out) {
     if (!out) return MT_E_ARG;
     int32_t r[MT_SEGQ_N];
     int32_t rc = seg_query(e, doc, 4, pos, 0, ref_seq, long_client, r);
     if (rc) return rc;
-    *out = r[0] == 1 ? r[1] : (pos == r[3] ? r[4] : -1);
+    *out = remote_pos(r, pos, false);
     return MT_OK;
 }
 
@@ -1045,7 +1058,7 @@ int32_t mt_engine_adjust_position(mt_engine* e, int64_t doc, int32_t pos, int32_
     int32_t r[MT_SEGQ_N];
     int32_t rc = seg_query(e, doc, 4, pos, 0, from_seq, long_client, r);
     if (rc) return rc;
-    *out = r[0] == 1 && !r[2] ? r[1] : -1;
+    *out = remote_pos(r, pos, true);
     return MT_OK;
 }
 
@@ -1080,6 +1093,224 @@ int64_t mt_engine_segment_ids(mt_engine* e, int64_t doc, int32_t* out, int64_t c
     int32_t rc = e->ops->segids(e, doc, dbuf, out ? cap : 0, dn);
     if (rc) return -rc;
     return read_counted(e, dn, whole_count, dbuf, 8, out, cap);
+}
+
+/* ---- batched reads (mt_kernels.h k_lengths / k_text_sizes / k_texts / k_segs) ---------------------------------
+ * The queries of one call, grouped by the engine that holds their document (route, through chains of promotions),
+ * each group a contiguous run of `q` and one launch on its engine's stream. In a tiled engine the reads keep
+ * scratch in the document block, so the k-th query that names a document goes into the k-th launch there
+ * (launches on one stream run in order). All engines of a chain share the device: the queries and the results
+ * live in the root engine's buffers, and every result lands at the caller's query index (ReadQ.slot). */
+struct ReadPlan {
+    struct Run {
+        mt_engine* eng;
+        int64_t q0, n;
+    };
+    std::vector<ReadQ> q;
+    std::vector<Run> runs;
+};
+static int32_t read_plan(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* a, const int32_t* b,
+                         int32_t dflt, const int32_t* ref_seqs, const int32_t* long_clients, ReadPlan& p) {
+    if (m > (int64_t)0x7fffffff || !ref_seqs != !long_clients || (!docs && m > e->ndocs)) return MT_E_ARG;
+    std::vector<mt_engine*> chain;
+    for (mt_engine* x = e; x; x = x->over) chain.push_back(x);
+    std::vector<std::vector<ReadQ>> by(chain.size());
+    for (int64_t i = 0; i < m; i++) {
+        int64_t d = docs ? docs[i] : i;
+        if (d < 0 || d >= e->ndocs) return MT_E_ARG;
+        const int32_t lc = long_clients ? long_clients[i] : -1;
+        const int32_t floor = persp_floor(e, d, lc); /* on the engine the caller holds, before routing */
+        size_t depth = 0;
+        for (mt_engine* x = e; x->over && x->pro[(size_t)d] >= 0; x = x->over, depth++) d = x->pro[(size_t)d];
+        by[depth].push_back(ReadQ{d, ref_seqs ? ref_seqs[i] : 0, lc, floor, a ? a[i] : dflt, b ? b[i] : dflt, (int32_t)i});
+    }
+    p.q.reserve((size_t)m);
+    for (size_t k = 0; k < chain.size(); k++) {
+        std::vector<ReadQ>& g = by[k];
+        if (g.empty()) continue;
+        if (chain[k]->profile != P_HUGE) {
+            p.runs.push_back({chain[k], (int64_t)p.q.size(), (int64_t)g.size()});
+            p.q.insert(p.q.end(), g.begin(), g.end());
+            continue;
+        }
+        std::vector<int32_t> seen((size_t)chain[k]->ndocs, 0), round(g.size());
+        int32_t rounds = 0;
+        for (size_t i = 0; i < g.size(); i++) rounds = std::max(rounds, (round[i] = seen[(size_t)g[i].doc]++) + 1);
+        for (int32_t r = 0; r < rounds; r++) {
+            const int64_t q0 = (int64_t)p.q.size();
+            for (size_t i = 0; i < g.size(); i++)
+                if (round[i] == r) p.q.push_back(g[i]);
+            p.runs.push_back({chain[k], q0, (int64_t)p.q.size() - q0});
+        }
+    }
+    return MT_OK;
+}
+extern "C++" {
+/* one launch per run of the plan: launch(engine, stream, its queries on the device, their count). What the root
+ * engine's stream has copied to the device is there before a child's stream reads it, and the root waits on each
+ * child's stream before it copies anything back. */
+template <class F>
+static int32_t read_launch(mt_engine* e, const ReadPlan& p, const ReadQ* dq, F&& launch) {
+    bool children = false;
+    for (const ReadPlan::Run& r : p.runs) children |= r.eng != e;
+    if (children) HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (const ReadPlan::Run& r : p.runs) {
+        int32_t rc = launch(r.eng, r.eng->stream, dq + r.q0, r.n);
+        if (rc) {
+            if (r.eng != e) e->err = r.eng->err;
+            return rc;
+        }
+    }
+    for (size_t i = 0; children && i < p.runs.size(); i++)
+        if (p.runs[i].eng != e && (i == 0 || p.runs[i].eng != p.runs[i - 1].eng))
+            HIPCHK(e, hipStreamSynchronize(p.runs[i].eng->stream));
+    return MT_OK;
+}
+}
+static size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+int32_t mt_engine_get_lengths(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* ref_seqs,
+                              const int32_t* long_clients, int32_t* len_out, int32_t* status_out) {
+    if (!e || m < 0) return MT_E_ARG;
+    if (m == 0) return MT_OK;
+    if (!len_out || (!status_out && long_clients)) return MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, nullptr, nullptr, 0, ref_seqs, long_clients, p);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m);
+    if ((rc = ensure(e, e->rq, qb + 8 * (size_t)m))) return rc;
+    ReadQ* dq = (ReadQ*)e->rq.p;
+    int32_t* dlen = (int32_t*)((uint8_t*)e->rq.p + qb);
+    int32_t* dst = dlen + m;
+    HIPCHK(e, hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->lengths(x, s, n, q, dlen, dst);
+    });
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(len_out, dlen, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    if (status_out) HIPCHK(e, hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MT_OK;
+}
+
+int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* ref_seqs,
+                            const int32_t* long_clients, const int32_t* starts, const int32_t* ends,
+                            const uint16_t* placeholder, int32_t placeholder_len, int64_t* off_out,
+                            int32_t* status_out, uint16_t* out, int64_t cap) {
+    if (!e || m < 0 || cap < 0 || placeholder_len < 0 || placeholder_len > 4096 || (placeholder_len > 0 && !placeholder))
+        return -MT_E_ARG;
+    if (placeholder_len == 1 && placeholder[0] == '*') return -MT_E_UNSUPPORTED; /* Marker.toString() */
+    if (m == 0) return 0;
+    if (!off_out || (!status_out && long_clients)) return -MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, starts, ends, MT_TEXT_DEFAULT, ref_seqs, long_clients, p);
+    if (rc) return -rc;
+    if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
+    /* the queries, their sizes, the offsets, the statuses, the placeholder */
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), sb = up16(8 * (size_t)m), ob = up16(8 * ((size_t)m + 1)),
+                 tb = up16(4 * (size_t)m), phb = up16(2 * (size_t)placeholder_len);
+    if ((rc = ensure(e, e->rq, qb + sb + ob + tb + phb))) return -rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    int64_t* dsize = (int64_t*)(base + qb);
+    int64_t* doff = (int64_t*)(base + qb + sb);
+    int32_t* dst = (int32_t*)(base + qb + sb + ob);
+    uint16_t* dph = (uint16_t*)(base + qb + sb + ob + tb);
+    if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    if (placeholder_len > 0 &&
+        hipMemcpyAsync(dph, placeholder, 2 * (size_t)placeholder_len, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->text_sizes(x, s, n, q, placeholder_len, dsize, dst);
+    });
+    if (rc) return -rc;
+    /* the exclusive prefix sum of the sizes, on the host: they come back in one copy */
+    if (hipMemcpyAsync(off_out + 1, dsize, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    if (status_out && hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    off_out[0] = 0;
+    for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
+    const int64_t total = off_out[m];
+    if (!out || total > cap || total == 0) return total; /* all or nothing */
+    if (ensure(e, e->tmp, 2 * (size_t)total)) return -MT_E_NOMEM;
+    uint16_t* dout = (uint16_t*)e->tmp.p;
+    if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    const bool packed = e->texts_packed;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->texts(x, s, n, q, dph, placeholder_len, doff, dout, packed);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(out, dout, 2 * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    return total;
+}
+
+/* k_segs over m queries: res[i * MT_SEGQ_N ..] = query i's words; status_out[i] = MT_E_UNSUPPORTED for a refused one */
+static int32_t segs_read(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, const int32_t* ref_seqs,
+                         const int32_t* long_clients, int32_t mode, std::vector<int32_t>& res, int32_t* status_out) {
+    if (!pos || (!status_out && long_clients)) return MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, pos, nullptr, 0, ref_seqs, long_clients, p);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), rb = 4 * (size_t)m * MT_SEGQ_N;
+    if ((rc = ensure(e, e->rq, qb + rb))) return rc;
+    ReadQ* dq = (ReadQ*)e->rq.p;
+    int32_t* dres = (int32_t*)((uint8_t*)e->rq.p + qb);
+    HIPCHK(e, hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->segs(x, s, n, q, mode, dres);
+    });
+    if (rc) return rc;
+    res.resize((size_t)m * MT_SEGQ_N);
+    HIPCHK(e, hipMemcpyAsync(res.data(), dres, rb, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; status_out && i < m; i++)
+        status_out[i] = res[(size_t)i * MT_SEGQ_N] == 3 ? MT_E_UNSUPPORTED : MT_OK;
+    return MT_OK;
+}
+
+int32_t mt_engine_get_containing_segments(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                          const int32_t* ref_seqs, const int32_t* long_clients, mt_seg_ref* out,
+                                          int32_t* status_out) {
+    if (!e || m < 0) return MT_E_ARG;
+    if (m == 0) return MT_OK;
+    if (!out) return MT_E_ARG;
+    std::vector<int32_t> res;
+    int32_t rc = segs_read(e, m, docs, pos, ref_seqs, long_clients, 0, res, status_out);
+    if (rc) return rc;
+    for (int64_t i = 0; i < m; i++) seg_ref_of(&res[(size_t)i * MT_SEGQ_N], &out[i]);
+    return MT_OK;
+}
+
+static int32_t remote_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, const int32_t* seqs,
+                                const int32_t* long_clients, bool adjust, int32_t* out, int32_t* status_out) {
+    if (!e || m < 0) return MT_E_ARG;
+    if (m == 0) return MT_OK;
+    if (!out) return MT_E_ARG;
+    std::vector<int32_t> res;
+    int32_t rc = segs_read(e, m, docs, pos, seqs, long_clients, 4, res, status_out);
+    if (rc) return rc;
+    for (int64_t i = 0; i < m; i++) {
+        const int32_t* r = &res[(size_t)i * MT_SEGQ_N];
+        out[i] = r[0] == 3 ? -1 : remote_pos(r, pos[i], adjust);
+    }
+    return MT_OK;
+}
+int32_t mt_engine_resolve_remote_client_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                                  const int32_t* ref_seqs, const int32_t* long_clients,
+                                                  int32_t* out, int32_t* status_out) {
+    return remote_positions(e, m, docs, pos, ref_seqs, long_clients, false, out, status_out);
+}
+int32_t mt_engine_adjust_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                   const int32_t* from_seqs, const int32_t* long_clients, int32_t* out,
+                                   int32_t* status_out) {
+    return remote_positions(e, m, docs, pos, from_seqs, long_clients, true, out, status_out);
 }
 
 /* where the host reads a document's block directly: the block (its header is at the start), the DState at the head

@@ -41,7 +41,7 @@ class _Caps(ctypes.Structure):
 
 
 _LIB = None
-MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS = 1, 2, 3  # include/mt_engine.h
+MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS, MT_VAR_TEXTS_PACKED = 1, 2, 3, 4  # include/mt_engine.h
 
 
 def lib() -> ctypes.CDLL:
@@ -106,6 +106,12 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_get_marker_from_id.argtypes = [vp, i64, i32, i32, ctypes.POINTER(SegRef)]
         L.mt_engine_segment_ids.argtypes = [vp, i64, vp, i64]
         L.mt_engine_segment_ids.restype = i64
+        L.mt_engine_get_lengths.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+        L.mt_engine_get_texts.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64]
+        L.mt_engine_get_texts.restype = i64
+        L.mt_engine_get_containing_segments.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+        L.mt_engine_resolve_remote_client_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+        L.mt_engine_adjust_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_ndocs.argtypes = [vp]
         L.mt_engine_ndocs.restype = i64
         _LIB = L
@@ -311,6 +317,101 @@ class Engine:
         buf = np.zeros(max(n, 1), "<u2")
         self.L.mt_engine_get_text_range(self.h, doc, ref_seq, long_client, pp, pl, a, b, _p(buf), n)
         return buf[:n].tobytes().decode("utf-16-le")
+
+    # ---- batched reads (include/mt_engine.h): many queries per launch, one stream wait per call ----
+    def _queries(self, docs, ref_seqs, long_clients):
+        """(m, docs, ref_seqs, long_clients) as the C ABI takes them: docs None = every document; the perspective
+        arrays both None = the local view for every query, else one entry per query (a scalar is broadcast)."""
+        d = None if docs is None else np.ascontiguousarray(docs, np.int64)
+        m = self.ndocs if d is None else len(d)
+        if ref_seqs is None and long_clients is None:
+            return m, d, None, None
+
+        def per_query(x, dflt):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(dflt if x is None else x, np.int32), (m,)))
+        return m, d, per_query(ref_seqs, 0), per_query(long_clients, -1)
+
+    @staticmethod
+    def _pn(a):
+        return None if a is None else _p(a)
+
+    def get_lengths(self, docs=None, ref_seqs=None, long_clients=None):
+        """getLength under each query's perspective (mt_engine_get_lengths): (lengths, status), status[i] 0 or
+        the MT_E_* code get_length would have raised for query i (its length is then 0)."""
+        m, d, rs, lc = self._queries(docs, ref_seqs, long_clients)
+        n, st = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        if m:
+            self._check(self.L.mt_engine_get_lengths(self.h, m, self._pn(d), self._pn(rs), self._pn(lc), _p(n), _p(st)),
+                        "get_lengths")
+        return n, st
+
+    def get_texts_units(self, docs=None, ref_seqs=None, long_clients=None, placeholder: str = "", starts=None,
+                        ends=None):
+        """mt_engine_get_texts as arrays: (units, off, status); query i's UTF-16 units are units[off[i]:off[i+1]].
+        One size query and one fill."""
+        m, d, rs, lc = self._queries(docs, ref_seqs, long_clients)
+        ph = np.frombuffer(placeholder.encode("utf-16-le"), "<u2").copy() if placeholder else None
+
+        def rng(x):
+            if x is None:
+                return None
+            return np.ascontiguousarray([TEXT_DEFAULT if v is None else v for v in x], np.int32)
+        a, b = rng(starts), rng(ends)
+        off, st = np.zeros(m + 1, np.int64), np.zeros(m, np.int32)
+        if not m:
+            return np.zeros(0, "<u2"), off, st
+
+        def call(out, cap):
+            n = self.L.mt_engine_get_texts(self.h, m, self._pn(d), self._pn(rs), self._pn(lc), self._pn(a),
+                                           self._pn(b), self._pn(ph), 0 if ph is None else len(ph), _p(off), _p(st),
+                                           out, cap)
+            if n < 0:
+                raise EngineError(f"get_texts failed {n}", -n)
+            return n
+        n = call(None, 0)
+        buf = np.zeros(max(n, 1), "<u2")
+        if n and call(_p(buf), n) != n:
+            raise EngineError("get_texts size changed")
+        return buf[:n], off, st
+
+    def get_texts(self, docs=None, ref_seqs=None, long_clients=None, placeholder: str = "", starts=None, ends=None):
+        """getText(refSeq, clientId, placeholder, start, end) per query (mt_engine_get_texts): (list of str,
+        status); a query whose status is not 0 has the empty string. starts / ends: None, or one entry per query
+        (an entry None = getValidRange's default)."""
+        units, off, st = self.get_texts_units(docs, ref_seqs, long_clients, placeholder, starts, ends)
+        raw = units.tobytes()
+        return [raw[2 * off[i]:2 * off[i + 1]].decode("utf-16-le") for i in range(len(st))], st
+
+    def _positions(self, fn, what, pos, docs, seqs, long_clients):
+        m, d, rs, lc = self._queries(docs, seqs, long_clients)
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.int32), (m,)))
+        out, st = np.full(m, -1, np.int32), np.zeros(m, np.int32)
+        if m:
+            self._check(fn(self.h, m, self._pn(d), _p(p), self._pn(rs), self._pn(lc), _p(out), _p(st)), what)
+        return out, st
+
+    def get_containing_segments(self, pos, docs=None, ref_seqs=None, long_clients=None):
+        """getContainingSegment per query (mt_engine_get_containing_segments): (a ctypes array of SegRef, rid -1
+        where the reference returns `segment: undefined`; status)."""
+        m, d, rs, lc = self._queries(docs, ref_seqs, long_clients)
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.int32), (m,)))
+        out, st = (SegRef * max(m, 1))(), np.zeros(m, np.int32)
+        if m:
+            self._check(self.L.mt_engine_get_containing_segments(self.h, m, self._pn(d), _p(p), self._pn(rs),
+                                                                 self._pn(lc), out, _p(st)), "get_containing_segments")
+        return out, st
+
+    def resolve_remote_client_positions(self, pos, ref_seqs, long_clients, docs=None):
+        """resolveRemoteClientPosition per query (mt_engine_resolve_remote_client_positions): (positions, -1 =
+        undefined; status)."""
+        return self._positions(self.L.mt_engine_resolve_remote_client_positions, "resolve_remote_client_positions",
+                               pos, docs, ref_seqs, long_clients)
+
+    def adjust_positions(self, pos, from_seqs, long_clients, docs=None):
+        """PermutationVector.adjustPosition per query (mt_engine_adjust_positions): (positions, -1 = undefined;
+        status)."""
+        return self._positions(self.L.mt_engine_adjust_positions, "adjust_positions", pos, docs, from_seqs,
+                               long_clients)
 
     def get_items(self, doc: int, start: int, end: Optional[int] = None) -> list:
         """SharedSequence.getItems(start, end) (sequence sharedSequence.ts:150-183) of a SubSequence document in the

@@ -112,6 +112,10 @@ export declare class ReplayEngine {
     flush(): void;
     /** per-document FNV-1a-64 digests of the canonical segment dump */
     digests(): BigUint64Array;
+    /** Client.getLength() of every listed document (default: all), one launch for the list (mt_engine_get_lengths) */
+    getLengths(docs?: number[]): Int32Array;
+    /** Client.getText() of every listed document (default: all), two launches for the list (mt_engine_get_texts) */
+    getTexts(docs?: number[]): string[];
     longIndex(name: string): number;
 }
 

@@ -389,6 +389,20 @@ class ReplayEngine {
     }
 
     digests() { this.flush(); return addon.digests(this.h); }
+
+    /* Client.getLength() / Client.getText() of every listed document (all of them by default) in one launch each
+     * (mt_engine_get_lengths / mt_engine_get_texts) instead of one per GpuClient; a listed document with a latched
+     * error throws, as its client's read would */
+    getLengths(docs) { this.flush(); checkDocs(this, docs); return addon.getLengths(this.h, docs); }
+
+    getTexts(docs) { this.flush(); checkDocs(this, docs); return addon.getTexts(this.h, docs); }
+}
+
+/* the latched errors of the listed documents (undefined: all), read in one call */
+function checkDocs(engine, docs) {
+    const [err, errOp] = addon.errors(engine.h);
+    for (const d of docs === undefined ? err.keys() : docs)
+        if (err[d] !== 0) throw new Error(`document ${d}: ${ERRORS[err[d]] || err[d]} at event ${errOp[d]}`);
 }
 
 /* The MergeTree-level calls of one replica with explicit (refSeq, clientId, seq) (mergeTree.ts:2001-2031,

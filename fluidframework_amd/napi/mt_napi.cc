@@ -568,6 +568,112 @@ static napi_value remote_pos(napi_env env, napi_callback_info info, bool adjust)
 static napi_value js_resolve_remote(napi_env env, napi_callback_info info) { return remote_pos(env, info, false); }
 static napi_value js_adjust_position(napi_env env, napi_callback_info info) { return remote_pos(env, info, true); }
 
+/* ---- batched reads (include/mt_engine.h): one launch for every listed document ---- */
+/* an optional array of document ids: undefined = every document (docs stays empty, *all = true) */
+static bool docs_of(napi_env env, napi_value v, std::vector<int64_t>* docs, bool* all) {
+    *all = opt_undefined(env, v);
+    if (*all) return true;
+    uint32_t n = 0;
+    if (napi_get_array_length(env, v, &n) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "docs: expected an array of document ids");
+        return false;
+    }
+    docs->resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        napi_value x;
+        if (napi_get_element(env, v, i, &x) != napi_ok || !i64_of(env, x, &(*docs)[i])) return false;
+    }
+    return true;
+}
+static napi_value i32_array(napi_env env, const int32_t* src, size_t n) {
+    napi_value ab, ta;
+    void* p;
+    NAPI_OK(napi_create_arraybuffer(env, 4 * n, &p, &ab));
+    if (n) memcpy(p, src, 4 * n);
+    NAPI_OK(napi_create_typedarray(env, napi_int32_array, n, ab, 0, &ta));
+    return ta;
+}
+
+/* getLengths(h[, docs]) -> Int32Array: Client.getLength of each listed document (mt_engine_get_lengths) */
+static napi_value js_get_lengths(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    size_t argc = 2;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1) {
+        napi_throw_type_error(env, nullptr, "missing arguments");
+        return nullptr;
+    }
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = true;
+    if (!e || (argc > 1 && !docs_of(env, argv[1], &docs, &all))) return nullptr;
+    const int64_t m = all ? mt_engine_ndocs(e) : (int64_t)docs.size();
+    std::vector<int32_t> len((size_t)m + 1);
+    int32_t rc = mt_engine_get_lengths(e, m, all ? nullptr : docs.data(), nullptr, nullptr, len.data(), nullptr);
+    if (rc) return throw_status(env, e, rc, "mt_engine_get_lengths");
+    return i32_array(env, len.data(), (size_t)m);
+}
+
+/* getTexts(h[, docs]) -> string[]: Client.getText of each listed document (mt_engine_get_texts: a size query and a
+ * fill, two launches each, however many documents) */
+static napi_value js_get_texts(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    size_t argc = 2;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1) {
+        napi_throw_type_error(env, nullptr, "missing arguments");
+        return nullptr;
+    }
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = true;
+    if (!e || (argc > 1 && !docs_of(env, argv[1], &docs, &all))) return nullptr;
+    const int64_t m = all ? mt_engine_ndocs(e) : (int64_t)docs.size();
+    const int64_t* dp = all ? nullptr : docs.data();
+    std::vector<int64_t> off((size_t)m + 1, 0);
+    int64_t n = mt_engine_get_texts(e, m, dp, nullptr, nullptr, nullptr, nullptr, nullptr, 0, off.data(), nullptr, nullptr, 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_get_texts");
+    std::vector<uint16_t> buf((size_t)n + 1);
+    int64_t n2 = mt_engine_get_texts(e, m, dp, nullptr, nullptr, nullptr, nullptr, nullptr, 0, off.data(), nullptr,
+                                     buf.data(), n);
+    if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_get_texts");
+    napi_value out;
+    NAPI_OK(napi_create_array_with_length(env, (size_t)m, &out));
+    for (int64_t i = 0; i < m; i++) {
+        napi_value s;
+        NAPI_OK(napi_create_string_utf16(env, (const char16_t*)buf.data() + off[(size_t)i],
+                                         (size_t)(off[(size_t)i + 1] - off[(size_t)i]), &s));
+        NAPI_OK(napi_set_element(env, out, (uint32_t)i, s));
+    }
+    return out;
+}
+
+/* adjustPositions(h, docs, pos, fromSeqs, longClients) -> [Int32Array positions (-1: undefined), Int32Array status]:
+ * PermutationVector.adjustPosition for a batch of remote ops (mt_engine_adjust_positions); docs is an array of
+ * document ids, the others Int32Arrays of its length */
+static napi_value js_adjust_positions(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = false;
+    if (!e || !docs_of(env, argv[1], &docs, &all)) return nullptr;
+    void* p[3];
+    size_t len[3];
+    for (int i = 0; i < 3; i++)
+        if (!view_of(env, argv[2 + i], &p[i], &len[i], napi_int32_array)) return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (len[0] != m || len[1] != m || len[2] != m) return throw_status(env, e, MT_E_ARG, "adjustPositions (array lengths)");
+    std::vector<int32_t> out(m + 1, -1), st(m + 1, 0);
+    int32_t rc = mt_engine_adjust_positions(e, (int64_t)m, all ? nullptr : docs.data(), (const int32_t*)p[0],
+                                            (const int32_t*)p[1], (const int32_t*)p[2], out.data(), st.data());
+    if (rc) return throw_status(env, e, rc, "mt_engine_adjust_positions");
+    napi_value res, a = i32_array(env, out.data(), m), b = i32_array(env, st.data(), m);
+    if (!a || !b) return nullptr;
+    NAPI_OK(napi_create_array_with_length(env, 2, &res));
+    NAPI_OK(napi_set_element(env, res, 0, a));
+    NAPI_OK(napi_set_element(env, res, 1, b));
+    return res;
+}
+
 /* handleToPosition(h, doc, handle, localSeq) -> number */
 static napi_value js_handle_to_position(napi_env env, napi_callback_info info) {
     napi_value argv[4];
@@ -661,7 +767,8 @@ static napi_value init(napi_env env, napi_value exports) {
                {"resolveRemoteClientPosition", js_resolve_remote}, {"adjustPosition", js_adjust_position},
                {"handleToPosition", js_handle_to_position}, {"getMarkerFromId", js_marker_from_id},
                {"dump", js_dump},           {"segmentIds", js_segment_ids},
-               {"submitDocs", js_submit_docs}, {"docError", js_doc_error}, {"setValueKinds", js_set_value_kinds}};
+               {"submitDocs", js_submit_docs}, {"docError", js_doc_error}, {"setValueKinds", js_set_value_kinds},
+               {"getLengths", js_get_lengths}, {"getTexts", js_get_texts}, {"adjustPositions", js_adjust_positions}};
     for (auto& f : fns) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.cb, nullptr, &fn));

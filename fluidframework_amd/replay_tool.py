@@ -253,7 +253,9 @@ def replay(log: Log, device: int = 0, **caps):
         if bad:
             i = bad[0]
             raise RuntimeError(f"replica {st.docs[i]} failed at record {err_op[i]}: error {err[i]}")
-        return [(p, c_, eng.get_text(i), eng.get_length(i),
+        texts, _ = eng.get_texts()  # every replica's text and length: one launch each, not one per replica
+        lengths, _ = eng.get_lengths()
+        return [(p, c_, texts[i], int(lengths[i]),
                  [st.interner.item_obj(u) for u in eng.get_items(i, 0)] if log.types.get(p) in SEQUENCE_TYPES else None)
                 for i, (p, c_) in enumerate(st.docs)]
     finally:

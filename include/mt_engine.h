@@ -134,8 +134,11 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *   MT_VAR_TILED_WIDE (0 | 1): the config-4 (tiled) kernel with the zamboni heap in HBM and the full window set
  *     (default 0: the narrow LDS-heap build, which promotes documents it cannot hold to the wide one).
  *   MT_VAR_CHUNK_DOCS (>= 0): documents per chunk of mt_engine_submit_run (0: automatic).
+ *   MT_VAR_TEXTS_PACKED (0 | 1): how mt_engine_get_texts' fill kernel copies: 1 = the wave writes each pass of 64
+ *     segments as one contiguous run, 0 = every lane copies its own segment's piece (the single-document read's
+ *     copy); takes effect at the next mt_engine_get_texts.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
-enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3 };
+enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -212,6 +215,46 @@ int32_t mt_engine_resolve_remote_client_position(mt_engine* e, int64_t doc, int3
  * matrix.ts:597-605): as resolveRemoteClientPosition for a segment that exists and is not removed, else -1. */
 int32_t mt_engine_adjust_position(mt_engine* e, int64_t doc, int32_t pos, int32_t from_seq, int32_t long_client,
                                   int32_t* out);
+/* ---- batched reads: m queries, one wave each, in one launch (two for the texts) and one stream wait --------
+ * Query i names document docs[i] (docs == NULL: documents 0..m-1, and then m <= ndocs) under the perspective
+ * (ref_seqs[i], long_clients[i]); both arrays NULL = the local view for every query, else both per query, with
+ * long_clients[i] < 0 = the local view, as in the single-document calls. The queries only read: the flat
+ * profiles' reads write nothing into the document block, so a document may appear several times, in any order
+ * (the tiled profile's position index keeps its search scratch in the block: the engine runs the queries that
+ * name one tiled document in successive launches, with the same results). status_out[i] is MT_OK or the code
+ * the single call would have returned for the query (MT_E_UNSUPPORTED: a perspective persp_refused names, or a
+ * placeholder run past PH_RUN_MAX); a failed query has length 0, a zero-length text, rid -1 or position -1, and
+ * does not fail the call. status_out may be NULL only when long_clients is NULL. The return value is for
+ * engine-level errors only (MT_E_ARG, MT_E_HIP, MT_E_NOMEM). m == 0 succeeds and touches nothing. Promoted
+ * documents answer from their engines, each on its own stream; results land at the caller's query index. The
+ * preconditions about a running replay and mt_engine_sync are those of the single-document reads. */
+/* MergeTree.getLength(refSeq, clientId) (mergeTree.ts:1610; Client.getLength, client.ts:1051) per query. */
+int32_t mt_engine_get_lengths(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* ref_seqs,
+                              const int32_t* long_clients, int32_t* len_out, int32_t* status_out);
+/* MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start, end) (textSegment.ts:154-186) per query:
+ * starts / ends NULL = MT_TEXT_DEFAULT for every query; one placeholder per call, with the limits and the "*"
+ * refusal of mt_engine_get_text_range. Returns the total in UTF-16 units (<0: -MT_E_*) and always fills
+ * off_out[0..m]: query i's text is out[off_out[i] .. off_out[i+1]). `out` is written only when the total fits
+ * cap: all or nothing, like mt_engine_dump; out == NULL is the size query. */
+int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* ref_seqs,
+                            const int32_t* long_clients, const int32_t* starts, const int32_t* ends,
+                            const uint16_t* placeholder, int32_t placeholder_len, int64_t* off_out,
+                            int32_t* status_out, uint16_t* out, int64_t cap);
+/* MergeTree.getContainingSegment(pos, refSeq, clientId) (mergeTree.ts:1656-1667) per query; out[i].rid = -1
+ * where there is no segment at pos[i]. */
+int32_t mt_engine_get_containing_segments(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                          const int32_t* ref_seqs, const int32_t* long_clients, mt_seg_ref* out,
+                                          int32_t* status_out);
+/* MergeTree.resolveRemoteClientPosition(pos, refSeq, clientId) (mergeTree.ts:2140-2160) per query; out[i] = -1
+ * for undefined. */
+int32_t mt_engine_resolve_remote_client_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                                  const int32_t* ref_seqs, const int32_t* long_clients,
+                                                  int32_t* out, int32_t* status_out);
+/* PermutationVector.adjustPosition(pos, fromSeq, clientId) (permutationvector.ts:185-196) per query: what a
+ * SharedMatrix host calls once per remote op (matrix.ts:597-605), for a batch of them; out[i] = -1 for undefined. */
+int32_t mt_engine_adjust_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
+                                   const int32_t* from_seqs, const int32_t* long_clients, int32_t* out,
+                                   int32_t* status_out);
 /* PermutationVector.handleToPosition(handle, localSeq) (permutationvector.ts:198-253; matrix.ts:532-533): the
  * segment whose allocated handles hold `handle` (walkAllSegments order), at findReconnectionPostition(segment,
  * localSeq) + offset (client.ts:675-705). MT_E_ARG if no segment holds it or local_seq is past the replica's
