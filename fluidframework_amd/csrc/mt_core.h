@@ -6392,6 +6392,183 @@ struct Replica {
           }
         }
     }
+    /* ---- the lane-parallel dump (the batched read, mt_kernels.h k_dump_sizes / k_dumps<true>) ---- */
+    /* one little-endian dword at p, which is 2-byte aligned: one store where p is 4-byte aligned, else two halves */
+    MT_HD static void put32(uint8_t* p, uint32_t v) {
+        if (((uintptr_t)p & 2) == 0) {
+            *(uint32_t*)p = v;
+        } else {
+            ((uint16_t*)p)[0] = (uint16_t)v;
+            ((uint16_t*)p)[1] = (uint16_t)(v >> 16);
+        }
+    }
+    /* packed_copy for pieces that each have a destination of their own: lane l's piece is base[src, src + len),
+     * written to dst[dof, dof + len) (dst 2-byte aligned; the pieces do not overlap; len = 0: none). Each piece
+     * is laid into a run of unit pairs that starts at the 4-byte boundary at or below its destination, the runs
+     * end to end over the lanes (vo, their exclusive scan: all even), so no pair spans two pieces and every pair
+     * is 4-byte aligned in dst. The lanes stride over the runs a pair each (one search per pair: the last lane
+     * with vo <= v, as packed_copy) and store a dword, or the one half that lies inside the piece (its first unit
+     * at an odd start, its last at an odd end). Wave-uniform control flow: every lane must call this with the
+     * same dst and base. */
+    MT_HD void scatter_copy(uint16_t* dst, int32_t dof, int32_t len, int32_t src, const uint16_t* base) {
+        const int32_t par = len > 0 ? (int32_t)(((uintptr_t)(dst + dof) >> 1) & 1) : 0;
+        int32_t vtot;
+        const int32_t vo = w.excl_scan(len > 0 ? (par + len + 1) & ~1 : 0, &vtot);
+        const int32_t dal = dof - par, sal = src - par, rng = (len << 1) | par; /* the run's first pair in dst / base */
+        for (int32_t b = 0; b < vtot; b += 2 * W::N) {
+            const int32_t v = b + 2 * w.lane();
+            int32_t L = 0, e = w.shfl(vo, 0);
+            for (int32_t st = W::N >> 1; st > 0; st >>= 1) {
+                int32_t c = w.shfl(vo, L + st);
+                if (c <= v) L += st, e = c;
+            }
+            const int32_t d = w.shfl(dal, L), sb = w.shfl(sal, L), r = w.shfl(rng, L);
+            const int32_t i = v - e, lo = r & 1, hi = lo + (r >> 1); /* the piece is units [lo, hi) of its run */
+            const bool in0 = v < vtot && i >= lo && i < hi, in1 = v < vtot && i + 1 >= lo && i + 1 < hi;
+            const uint32_t x0 = in0 ? base[sb + i] : 0, x1 = in1 ? base[sb + i + 1] : 0;
+            uint16_t* p = dst + d + i;
+            if (in0 && in1)
+                *(uint32_t*)p = x0 | (x1 << 16);
+            else if (in0)
+                p[0] = (uint16_t)x0;
+            else if (in1)
+                p[1] = (uint16_t)x1;
+        }
+    }
+    /* The canonical dump written by the whole wave: dump()'s bytes and return value. Per pass of 8 leaves x 8 rows
+     * (the gather of get_text_range) every lane sizes its row's record (4 + 32 + 4 noverlap + 4 + 4 nprops + 8 per
+     * derived value when the document has any + 4 for a handle + 2 len for a text-bearing row), an exclusive scan
+     * places the records, each lane writes its record's dwords (put32: records start 2-byte aligned) and the wave
+     * copies the pass's texts (scatter_copy). out == NULL only sizes. A pass is written only if it ends inside
+     * cap, the header only if the whole dump does: a window of exactly the returned size is filled, a smaller one
+     * is never overrun. Every lane must call this; the one-lane host build takes the serial path. */
+    MT_HD int64_t dump_wave(uint8_t* out, int64_t cap) {
+        if constexpr (W::N < MAXN * MAXN) {
+            return dump(out, cap);
+        } else {
+            static_assert(HT::K <= W::N, "a key slot per lane");
+            const int32_t l = w.lane();
+            const uint16_t* base = arena_base(zh->arenaSide);
+            const bool runD = run_doc(), dv = (zh->ndv & 0xFFFF) != 0;
+            const int32_t llen = out ? length_local() : 0;
+            /* ord: lane q holds the key slot of rank q by global key id (ties, which only unused slots have, by
+             * slot), so that the properties come out sorted in one pass over the slots */
+            int32_t ord = 0;
+            if (out) {
+                const int32_t key = l < HT::K ? (int32_t)keys[l] : 0x7fffffff;
+                int32_t rank = 0;
+                for (int k = 0; k < HT::K; k++) {
+                    int32_t x = keys[k];
+                    rank += (x < key || (x == key && k < l)) ? 1 : 0;
+                }
+                for (int k = 0; k < HT::K; k++)
+                    if (w.bcast(rank, k) == l) ord = k;
+            }
+            int64_t n = 24;
+            int32_t nsegs = 0, kbase = 0; /* rows, and leaves, before the pass */
+            int32_t k = 0;
+            bool more = kvalid(0);
+            while (more) {
+                const int32_t li = l >> 3, j = l & (MAXN - 1);
+                int32_t leaf = -1, nl = 0;
+                for (int32_t i = 0; i < MAXN && more; i++) {
+                    int32_t lf = leaf_at(k);
+                    if (i == li) leaf = lf;
+                    k = knext(k);
+                    more = kvalid(k);
+                    nl++;
+                }
+                const int32_t s = leaf >= 0 && j < nch[leaf] ? leaf * MAXN + j : -1;
+                uint8_t fl = 0;
+                int32_t nov = 0, np = 0, nd = 0, tl = 0, fixed = 0;
+                bool hnd = false;
+                if (s >= 0) {
+                    fl = z.flags(s);
+                    nov = ovl_count(s);
+                    if (fl & RF_PROPS)
+                        for (int q = 0; q < HT::K; q++) {
+                            int32_t v = cold(s).pv[q];
+                            if (v) np++;
+                            if (dv && v >= MT_VALUE_DERIVED && v < MT_VALUE_NAN) nd++;
+                        }
+                    hnd = (fl & RF_PERM) && cold(s).toff != 0;
+                    tl = (fl & RF_NOTEXT) ? 0 : z.len(s);
+                    fixed = 4 + 32 + 4 * nov + 4 + 4 * np + 8 * nd + (hnd ? 4 : 0);
+                }
+                int32_t tot;
+                const int32_t eo = w.excl_scan(fixed + 2 * tl, &tot);
+                nsegs += w.sum(s >= 0 ? 1 : 0);
+                if (out && n + tot <= cap) { /* wave-uniform */
+                    uint8_t* c = out + n + eo;
+                    if (s >= 0) {
+                        const bool rem = z.rseq(s) != NOREM;
+                        const uint32_t kind = (fl & RF_MARKER) ? MT_SEG_MARKER : (fl & RF_PERM) ? MT_SEG_PERM
+                                              : runD           ? MT_SEG_RUN
+                                                               : MT_SEG_TEXT;
+                        const uint32_t df = ((fl & RF_PROPS) ? MT_DF_HAS_PROPS : 0) | (rem ? MT_DF_REMOVED : 0) |
+                                            ((fl & RF_LSEQ) ? MT_DF_LSEQ : 0) | ((fl & RF_LRSEQ) ? MT_DF_LRSEQ : 0) |
+                                            (hnd ? MT_DF_HANDLE : 0);
+                        put32(c, (kind & 0xFF) | ((df & 0xFF) << 8) | ((uint32_t)(nov & 0xFF) << 16) |
+                                     ((uint32_t)z.ng(s) << 24));
+                        put32(c + 4, (uint32_t)z.len(s));
+                        put32(c + 8, (uint32_t)z.seq(s));
+                        put32(c + 12, (uint32_t)long_of_cli(s));
+                        put32(c + 16, rem ? (uint32_t)z.rseq(s) : 0);
+                        put32(c + 20, rem ? (uint32_t)long_of_rcli(s) : 0);
+                        put32(c + 24, (fl & RF_LSEQ) ? (uint32_t)cold(s).lseq : 0);
+                        put32(c + 28, (fl & RF_LRSEQ) ? (uint32_t)cold(s).lrseq : 0);
+                        put32(c + 32, (uint32_t)(kbase + li)); /* the leaf's index in the walk */
+                        c += 36;
+                        for (int32_t q = 0; q < nov; q++, c += 4) put32(c, (uint32_t)long_of((uint8_t)ovl_at(s, q)));
+                        put32(c, (uint32_t)(np & 0xFFFF) | ((fl & RF_MARKER) ? (uint32_t)(cold(s).toff & 0xFFFF) << 16 : 0));
+                        c += 4;
+                    }
+                    if (w.ballot(np > 0)) { /* the slots in key order: the loop and its broadcasts are wave-uniform */
+                        for (int q = 0; q < HT::K; q++) {
+                            const int32_t kq = w.bcast(ord, q);
+                            uint32_t v = np > 0 ? cold(s).pv[kq] : 0;
+                            if (!v) continue;
+                            if (v >= MT_VALUE_DERIVED && v < MT_VALUE_NAN)
+                                v = v < MT_VALUE_CONS0 ? MT_VALUE_STRCAT0 : MT_VALUE_CONS0;
+                            put32(c, (uint32_t)keys[kq] | (v << 16));
+                            c += 4;
+                        }
+                        if (w.ballot(nd > 0)) /* derived values' contents, in pair order */
+                            for (int q = 0; q < HT::K; q++) {
+                                const int32_t kq = w.bcast(ord, q);
+                                const int32_t v = nd > 0 ? cold(s).pv[kq] : 0;
+                                if (v < MT_VALUE_DERIVED || v >= MT_VALUE_NAN) continue;
+                                uint32_t a0, a1 = 0;
+                                if (v < MT_VALUE_CONS0) {
+                                    int32_t x = z.dvs[v - MT_VALUE_STRCAT0];
+                                    a0 = (uint32_t)x & 0xFFFF, a1 = (uint32_t)x >> 16;
+                                } else {
+                                    a0 = (uint32_t)z.dvc[v - MT_VALUE_CONS0];
+                                }
+                                put32(c, a0);
+                                put32(c + 4, a1);
+                                c += 8;
+                            }
+                    }
+                    if (hnd) put32(c, (uint32_t)cold(s).toff);
+                    scatter_copy((uint16_t*)(out + n), (eo + fixed) >> 1, tl, tl > 0 ? (int32_t)cold(s).toff : 0, base);
+                }
+                n += tot;
+                kbase += nl;
+            }
+            if (out && n <= cap && l < 6) {
+                const int32_t hv = l == 0   ? h.currentSeq
+                                   : l == 1 ? h.minSeq
+                                   : l == 2 ? zh->localSeq
+                                   : l == 3 ? llen
+                                   : l == 4 ? nsegs
+                                            : h.nleaf;
+                put32(out + 4 * l, (uint32_t)hv);
+            }
+            w.sync();
+            return n;
+        }
+    }
     MT_HD static uint64_t fnv(const uint8_t* p, int64_t n) {
         uint64_t h = MT_FNV_OFFSET;
         for (int64_t i = 0; i < n; i++) {

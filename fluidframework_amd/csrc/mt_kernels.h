@@ -814,6 +814,37 @@ __global__ __launch_bounds__(WG) void k_segs(Store<HT> st, int64_t m, const Read
         for (int i = 0; i < MT_SEGQ_N; i++) out[(int64_t)q.slot * MT_SEGQ_N + i] = res[i];
 }
 
+/* ---- batched dumps (mt_engine_dumps): no perspective, so no status; only q.doc and q.slot are read ---- */
+#ifndef MT_DUMPS_PARALLEL_DEFAULT
+#define MT_DUMPS_PARALLEL_DEFAULT true /* k_dumps' writer: Replica::dump_wave or the serial dump */
+#endif
+/* the byte size of query i's canonical dump (size[slot]): every lane sizes one row's record per pass, the wave
+ * sums them (Replica::dump_wave without a buffer); what Replica::dump(nullptr, 0) returns */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_dump_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int64_t* size) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int64_t n = r.dump_wave(nullptr, 0);
+    if (threadIdx.x == 0) size[q.slot] = n;
+}
+/* query i's dump into out[off[slot], off[slot + 1]) (the host's prefix sum of k_dump_sizes' sizes) and nowhere
+ * else. PAR: the whole wave writes (Replica::dump_wave); else lane 0 writes byte by byte (Replica::dump, what
+ * k_dump runs): the same bytes either way. */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_dumps(Store<HT> st, int64_t m, const ReadQ* qs, const int64_t* off,
+                                             uint8_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    if constexpr (PAR)
+        (void)r.dump_wave(out + o, cap);
+    else
+        (void)r.dump(out + o, cap);
+}
+
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
  * out[2i+1] = its generation; *n = the segment count (writes at most cap pairs) */
 template <class HT>
@@ -961,6 +992,7 @@ struct mt_engine {
     int32_t nvk = 0;
     std::vector<uint8_t> h_vkind;
     bool texts_packed = MT_TEXTS_PACKED_DEFAULT; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
+    bool dumps_parallel = MT_DUMPS_PARALLEL_DEFAULT; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
@@ -1018,6 +1050,9 @@ struct ProfOps {
     int32_t (*texts)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const uint16_t* dph, int32_t pl,
                      const int64_t* doff, uint16_t* dout, bool packed);
     int32_t (*segs)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, int32_t* dres);
+    int32_t (*dump_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize);
+    int32_t (*dumps)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff, uint8_t* dout,
+                     bool par);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1130,8 +1165,20 @@ struct Launch {
         hipLaunchKernelGGL((k_segs<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, mode, dres);
         return launch_check(e, "k_segs");
     }
+    static int32_t dump_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize) {
+        hipLaunchKernelGGL((k_dump_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dsize);
+        return launch_check(e, "k_dump_sizes");
+    }
+    static int32_t dumps(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff, uint8_t* dout,
+                         bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_dumps<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
+        else
+            hipLaunchKernelGGL((k_dumps<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
+        return launch_check(e, "k_dumps");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
-        return ProfOps{init, start_collab, replay, hdr,    digest,  dump,       length, text,
-                       seg,  refpos,       segids, lengths, text_sizes, texts,  segs};
+        return ProfOps{init,   start_collab, replay, hdr,     digest,     dump,  length, text,       seg,
+                       refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps};
     }
 };

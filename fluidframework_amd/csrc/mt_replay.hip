@@ -866,6 +866,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value != 0 && value != 1) return MT_E_ARG;
         e->texts_packed = value == 1;
         return MT_OK;
+    case MT_VAR_DUMPS_PARALLEL:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->dumps_parallel = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1246,6 +1250,48 @@ int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const 
     });
     if (rc) return -rc;
     if (hipMemcpyAsync(out, dout, 2 * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    return total;
+}
+
+int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap) {
+    if (!e || m < 0 || cap < 0) return -MT_E_ARG;
+    if (m == 0) return 0;
+    if (!off_out) return -MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, nullptr, nullptr, 0, nullptr, nullptr, p);
+    if (rc) return -rc;
+    if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
+    /* the queries, their sizes, the offsets */
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), sb = up16(8 * (size_t)m), ob = up16(8 * ((size_t)m + 1));
+    if ((rc = ensure(e, e->rq, qb + sb + ob))) return -rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    int64_t* dsize = (int64_t*)(base + qb);
+    int64_t* doff = (int64_t*)(base + qb + sb);
+    if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->dump_sizes(x, s, n, q, dsize);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(off_out + 1, dsize, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    off_out[0] = 0;
+    for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
+    const int64_t total = off_out[m];
+    if (!out || total > cap) return total; /* all or nothing */
+    if (ensure(e, e->tmp, (size_t)total)) return -MT_E_NOMEM;
+    uint8_t* dout = (uint8_t*)e->tmp.p;
+    if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    const bool par = e->dumps_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->dumps(x, s, n, q, doff, dout, par);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(out, dout, (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
     return total;
 }

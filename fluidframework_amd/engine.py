@@ -42,6 +42,7 @@ class _Caps(ctypes.Structure):
 
 _LIB = None
 MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS, MT_VAR_TEXTS_PACKED = 1, 2, 3, 4  # include/mt_engine.h
+MT_VAR_DUMPS_PARALLEL = 5
 
 
 def lib() -> ctypes.CDLL:
@@ -109,6 +110,8 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_get_lengths.argtypes = [vp, i64, vp, vp, vp, vp, vp]
         L.mt_engine_get_texts.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i64]
         L.mt_engine_get_texts.restype = i64
+        L.mt_engine_dumps.argtypes = [vp, i64, vp, vp, vp, i64]
+        L.mt_engine_dumps.restype = i64
         L.mt_engine_get_containing_segments.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_resolve_remote_client_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_adjust_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
@@ -381,6 +384,31 @@ class Engine:
         units, off, st = self.get_texts_units(docs, ref_seqs, long_clients, placeholder, starts, ends)
         raw = units.tobytes()
         return [raw[2 * off[i]:2 * off[i + 1]].decode("utf-16-le") for i in range(len(st))], st
+
+    def dumps_raw(self, docs=None):
+        """mt_engine_dumps as arrays: (bytes, off); query i's canonical dump is bytes[off[i]:off[i+1]], what
+        dump(docs[i]) returns. docs None = every document. One size query and one fill."""
+        m, d, _, _ = self._queries(docs, None, None)
+        off = np.zeros(m + 1, np.int64)
+        if not m:
+            return np.zeros(0, np.uint8), off
+
+        def call(out, cap):
+            n = self.L.mt_engine_dumps(self.h, m, self._pn(d), _p(off), out, cap)
+            if n < 0:
+                raise EngineError(f"dumps failed {n}", -n)
+            return n
+        n = call(None, 0)
+        buf = np.zeros(max(n, 1), np.uint8)
+        if call(_p(buf), n) != n:
+            raise EngineError("dumps size changed")
+        return buf[:n], off
+
+    def dumps(self, docs=None) -> list:
+        """The canonical dump of every query's document (mt_engine_dumps): a list of bytes."""
+        buf, off = self.dumps_raw(docs)
+        raw = buf.tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
 
     def _positions(self, fn, what, pos, docs, seqs, long_clients):
         m, d, rs, lc = self._queries(docs, seqs, long_clients)

@@ -116,6 +116,8 @@ export declare class ReplayEngine {
     getLengths(docs?: number[]): Int32Array;
     /** Client.getText() of every listed document (default: all), two launches for the list (mt_engine_get_texts) */
     getTexts(docs?: number[]): string[];
+    /** the canonical dump of every listed document (default: all), two launches for the list (mt_engine_dumps) */
+    dumps(docs?: number[]): Buffer[];
     longIndex(name: string): number;
 }
 

@@ -322,6 +322,16 @@ def emit_from_dump(dump: bytes, interner: ol.Interner, long_name, chunk_size: in
     return emit_v1(hdr, segs, interner, long_name, chunk_size)
 
 
+def emit_batch(eng, docs, interner: ol.Interner, long_name, legacy: bool = False, catchup: Optional[List[dict]] = None,
+               chunk_size: int = CHUNK_SIZE, catchup_blob: str = CATCHUP) -> List[dict]:
+    """The summaries of many documents of an engine from one batched dump (Engine.dumps: one size launch and one
+    fill launch for all of them): emit_from_dump per document of `docs` (None: every document), or
+    emit_legacy_from_dump with `legacy` (the same `catchup` for each)."""
+    if legacy:
+        return [emit_legacy_from_dump(d, interner, catchup, chunk_size, catchup_blob) for d in eng.dumps(docs)]
+    return [emit_from_dump(d, interner, long_name, chunk_size) for d in eng.dumps(docs)]
+
+
 # ---- load -------------------------------------------------------------------------------------
 def _blobs(tree: dict) -> Dict[str, str]:
     """path -> contents of a merge-tree snapshot tree; a SharedString's tree holds it under `content`."""

@@ -137,8 +137,12 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *   MT_VAR_TEXTS_PACKED (0 | 1): how mt_engine_get_texts' fill kernel copies: 1 = the wave writes each pass of 64
  *     segments as one contiguous run, 0 = every lane copies its own segment's piece (the single-document read's
  *     copy); takes effect at the next mt_engine_get_texts.
+ *   MT_VAR_DUMPS_PARALLEL (0 | 1): how mt_engine_dumps' fill kernel writes: 1 = every lane writes its own segment's
+ *     record in 2- and 4-byte stores and the wave copies the texts together, 0 = one lane writes byte by byte (the
+ *     single-document dump's writer); takes effect at the next mt_engine_dumps.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
-enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4 };
+enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4,
+       MT_VAR_DUMPS_PARALLEL = 5 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -240,6 +244,15 @@ int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const 
                             const int32_t* long_clients, const int32_t* starts, const int32_t* ends,
                             const uint16_t* placeholder, int32_t placeholder_len, int64_t* off_out,
                             int32_t* status_out, uint16_t* out, int64_t cap);
+/* The canonical dump (mt_oplog.h) of every query's document: every segment in walkAllSegments order
+ * (mergeTree.ts:3002-3016), what SnapshotV1.extractSync reads to write a summary (snapshotV1.ts:156-234). There is no
+ * perspective and so no per-query status; docs[i] may be in any order and may repeat. Returns the total byte
+ * count (<0: -MT_E_*; a document id out of range: -MT_E_ARG) and always fills off_out[0..m], in bytes: query i's
+ * dump is out[off_out[i] .. off_out[i+1]), byte for byte what mt_engine_dump returns for that document; the
+ * windows are contiguous and unpadded (so a window may start at 2 mod 4). `out` is written only when the total
+ * fits cap: all or nothing, like mt_engine_get_texts; out == NULL is the size query. m == 0 returns 0 and
+ * touches nothing. */
+int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap);
 /* MergeTree.getContainingSegment(pos, refSeq, clientId) (mergeTree.ts:1656-1667) per query; out[i].rid = -1
  * where there is no segment at pos[i]. */
 int32_t mt_engine_get_containing_segments(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,
