@@ -372,6 +372,43 @@ def make_combine(node: str) -> None:
                                 "by tools/ref_replay.mjs (--combine-watch for first / prefix)"))
 
 
+def make_zamboni(node: str) -> None:
+    """tests/golden/refzamboni.npz: the hand-built zamboni edge logs (tests/zamboni_logs.py: append rules on long rows,
+    newlines, markers, prevSegment resets, properties past 8 keys, leaf boundaries, pack) replayed by the reference:
+    per document its digest, its whole canonical dump, the word count and FNV-1a-64 of its delta / maintenance stream
+    (APPEND and UNLINK order) and the SHA-256 of its SnapshotV1 summary at the end of the log. Every case's witness
+    must hold on the reference's dump."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_client as oc
+    import zamboni_logs as zl
+    cs = zl.cases()
+    b = zl.batch(cs)
+    it = cs[0].log.interner
+    cuts = [int(n) for n in np.diff(b.op_off)]  # summarized at the end of the log
+    d = os.path.join(SCRATCH, "zamboni")
+    dumps, info, secs, (trees, loaded, tail_err, tail_msgs, load_err, load_msgs) = run_reference(
+        b, d, node, cuts, interner=it, extra=("--deltas",))
+    for c, x in zip(cs, dumps):
+        if not c.witness(*ol.parse_dump(x)):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+    words = np.fromfile(os.path.join(d, "ref_deltas.bin"), "<i4")
+    woff = np.fromfile(os.path.join(d, "ref_delta_off.bin"), "<i8")
+    per = [words[woff[i]: woff[i + 1]] for i in range(b.ndocs)]
+    digests = np.asarray([fnv1a64(x) for x in dumps], np.uint64)
+    _, odig, oerr = oc.replay_batch(b)
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refzamboni.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=digests, dumps=np.frombuffer(b"".join(dumps), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(x) for x in dumps])]).astype(np.int64),
+        delta_nwords=np.diff(woff).astype(np.int64), delta_hashes=np.asarray([words_fnv(x) for x in per], np.uint64),
+        snap_sha256=np.asarray([hashlib.sha256(canonical_tree(t).encode()).hexdigest() for t in trees]),
+        source=("packages/dds/merge-tree/src + sequence sharedSequence.ts SubSequence + matrix permutationvector.ts "
+                "(reference, type-erased by tools/ts_erase.py) under node by tools/ref_replay.mjs --deltas with "
+                "snapshots.json; logs: tests/zamboni_logs.py"))
+    print(f"refzamboni: {b.ndocs} docs, {b.nops} records, every witness holds; oracle agrees on "
+          f"{int((odig == digests).sum())}/{b.ndocs} digests; {len(load_msgs)} summaries do not load", flush=True)
+
+
 def make_refentry(node: str) -> None:
     """tests/golden/refentry_kat.npz: the refsByOffset-entry KATs (tests/refs_entry_logs.py) replayed by the
     reference: LocalReference.toPosition() of every reference (-2: addLocalReference threw) and the digests."""
@@ -1046,11 +1083,15 @@ def main() -> None:
     ap.add_argument("--persp", action="store_true", help="write the past-perspective read fixtures (refpersp_*.npz) only")
     ap.add_argument("--replaytool", action="store_true", help="write the client replay tool fixture only")
     ap.add_argument("--subseq", action="store_true", help="write the SubSequence fixtures (refsubseq_*.npz) only")
+    ap.add_argument("--zamboni", action="store_true", help="write the zamboni edge-case fixture (refzamboni.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ts_erase.py"), "--out", ERASED], check=True)
     if args.sessions:
         make_sessions(args.node)
+        return
+    if args.zamboni:
+        make_zamboni(args.node)
         return
     if args.subseq:
         make_subseq(args.node)
