@@ -1,0 +1,401 @@
+"""Range edits that span many leaves against the REFERENCE (tests/golden/refranges.npz from
+tools/make_ref_goldens.py --ranges over tests/range_logs.py).
+
+The generator never removes more than 16 units or inserts more than 8, so no other fixture holds a remove or an
+annotate over more than two or three leaves, and the lane-parallel code that serves a wide one (range_op's find pass
+and visit loop over 256-slot wave blocks, remove_run, ack / ack_rows over more than 64 member rows, the tiled
+profile's window set past the narrow build's 2,048 entries) is compiled for the GPU only. The case list is the
+docstring of tests/range_logs.py. Every comparison is byte-exact.
+
+The fixture keeps whole dumps only of the documents that end with fewer than 100 rows; for the others the oracle's dump stands in once
+its digest (FNV-1a-64 of the dump) equals the reference's, which the CPU tier asserts for every case.
+
+CPU tier: the logs regenerate to the fixture's SHA-256; every witness holds; a census proves the widths are there
+and that the generator fixtures have none; the oracle, the host core under every profile's capacities (with and
+without delta stream and local references) and snapshot.emit equal the reference; the cap cases give their stated
+outcome. GPU tier: every kernel build replays all fitting cases in one batch to the reference's digests, dumps
+(single and batched, both writers), delta streams, lengths and texts, in one submit and in two."""
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+from fluidframework_amd import oplog as ol
+from fluidframework_amd import snapshot as sn
+import core_host
+import oracle_client as oc
+import range_logs as rl
+from make_goldens_sha import log_sha
+from test_ref_zamboni import BUILD_IDS, BUILDS, MT_VAR_DUMPS_PARALLEL, _check_state, caps_tuple, profile_caps
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CASES = rl.cases()
+CAPS = rl.caps()
+EVERY = CASES + CAPS
+NAMES = [c.name for c in EVERY]
+MT_E_CAPACITY = 5
+# what each cap case does (range_logs.py "Caps"): "digest" = it ends equal to the reference in the
+# profile (after promotion where the profile is too small), "capacity" = MT_E_CAPACITY latched at the record that
+# needs the room (Case.cut), in every profile it can reach
+CAP_OUTCOME = {"cap_window_4200": "capacity", "cap_overlap_80x10": "capacity", "cap_group_small": "digest"}
+# the documents a build must hand to a larger one (and no others): build id prefix -> case names
+PROMOTED = {"small": {"cap_group_small"}, "tiled-narrow": {"t_settled_2060"}}
+
+
+def fixture():
+    return np.load(os.path.join(GOLDEN, "refranges.npz"), allow_pickle=False)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_dumps():
+    """the oracle's dump of every case, once (shared, never changed)"""
+    b = rl.batch(EVERY)
+    out = []
+    for d, c in enumerate(EVERY):
+        o = oc.OracleClient(c.log.interner)
+        o.start_collab(c.log.local_long_id)
+        assert o.replay_arrays(*b.doc(d)) == 0, c.name
+        out.append((o.dump(), o.digest()))
+    return out
+
+
+def ref_dump(z, d: int) -> bytes:
+    """the reference's dump of fixture document d: stored, or the oracle's once its digest is the reference's"""
+    keep = [int(x) for x in z["keep"]]
+    if d in keep:
+        k = keep.index(d)
+        return z["dumps"][z["dump_off"][k]: z["dump_off"][k + 1]].tobytes()
+    dump, dig = _oracle_dumps()[d]
+    assert dig == int(z["digests"][d]), f"{NAMES[d]}: the oracle differs from the reference"
+    return dump
+
+
+def fitting(profile: str, perm_only: bool = False, cases=None, refs: bool = False):
+    """(indices into the fixture, the cases) that fit a profile; the reference cases (MT_OP_REF records) only where
+    the replay keeps local references (`refs`: rcap > 0)"""
+    cases = CASES if cases is None else cases
+    idx = [NAMES.index(c.name) for c in cases if profile in c.profiles and (not perm_only or c.kind == "perm")
+           and (refs or c.name not in rl.REF_NAMES)]
+    return idx, [EVERY[i] for i in idx]
+
+
+def test_logs_regenerate_to_the_fixture():
+    z = fixture()
+    assert [str(n) for n in z["names"]] == NAMES
+    assert log_sha(rl.batch(EVERY)) == str(z["log_sha256"]), "tests/range_logs.py no longer builds the fixture's logs"
+    assert len(z["digests"]) == len(EVERY) == len(z["snap_sha256"]) == len(z["delta_hashes"]) == len(z["nrows"])
+    assert [int(d) for d in z["keep"]] == [d for d in range(len(EVERY)) if int(z["nrows"][d]) < 100]
+    assert [NAMES[int(d)] for d in z["ref_docs"]] == list(rl.REF_NAMES) and z["ref_pos"].shape == (2, len(rl.REF_ROWS))
+
+
+def test_every_required_case_exists():
+    need = {f"w_{n}_{op}" for op in ("rem", "ann") for n in (
+        "leaf1", "leaf2", "l33", "edge256", "blocks3", "whole", "pastend", "empty_start", "empty_end", "empty_neg",
+        "sp_bb", "sp_bi", "sp_ib", "sp_ii", "fullleaf", "onerow", "quad0", "quad1", "quad2", "quad3")}
+    need |= {f"p_{n}_{op}" for op in ("rem", "ann") for n in (
+        "later_inserts", "own_later", "removed_before", "overlap", "invisible256", "twice", "markers", "items")}
+    need |= {f"w_{n}_{op}" for op in ("rem", "ann") for n in ("sameleaf", "sameleaf_full")} | set(rl.REF_NAMES)
+    need |= {"p_perm_rem", "p_unas", "p_unas_rev", "lg_ann_newkey", "lg_two_ann", "lg_ann_rem", "lg_regen", "af_drain",
+             "af_merge", "t_settled_2060"}
+    need |= {f"lg_{k}_{n}" for k in ("rem", "ann2", "annrw") for n in (65, 129, 300)}
+    assert need <= set(c.name for c in CASES)
+    assert tuple(c.name for c in CAPS) == rl.CAP_NAMES and set(CAP_OUTCOME) == set(rl.CAP_NAMES)
+    for c in EVERY:
+        stem = c.name[:-4] if c.name.endswith(("_rem", "_ann")) else c.name
+        stem = stem.rstrip("0123456789").rstrip("_") if stem.startswith(("w_quad", "lg_")) else stem
+        assert c.branch and callable(c.witness) and stem in rl.__doc__, c.name
+        if "tiled" != "".join(c.profiles):
+            assert len(c.log.ops) < 1500, c.name
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_witness_holds_on_the_reference_dump(name):
+    z = fixture()
+    d = NAMES.index(name)
+    hdr, segs = ol.parse_dump(ref_dump(z, d))
+    assert hdr["nsegs"] == int(z["nrows"][d])
+    assert EVERY[d].witness(hdr, segs), (EVERY[d].branch, hdr)
+
+
+def test_census_the_widths_are_in_the_fixture():
+    """what no generator log shows, counted in the reference's dumps: ops that touched more than 64 rows, rows on
+    both sides of a 256-slot boundary, more than 256 rows"""
+    z = fixture()
+    cen = rl.census([ol.parse_dump(ref_dump(z, d)) for d in range(len(EVERY))], EVERY[0].log.interner.values)
+    print(cen)
+    assert cen["over64"] >= 20 and cen["straddle"] >= 8 and cen["over256"] >= 4, cen
+
+
+@pytest.mark.parametrize("name", ["ref_c2_observer", "ref_c3_lagged", "ref_c4_scaled", "ref_c5_perm"])
+def test_census_the_generator_fixtures_have_none(name):
+    """the same census over the committed generator fixtures' dumps, and the widest range of their stored logs"""
+    from fluidframework_amd import gen
+    z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    off = z["keep_dump_off"]
+    parsed = [ol.parse_dump(z["keep_dumps"][off[i]: off[i + 1]].tobytes()) for i in range(len(off) - 1)]
+    assert len(parsed) >= 1 and sum(len(s) for _, s in parsed) > 100
+    cen = rl.census(parsed, gen.generator_interner().values)
+    assert cen["over64"] == cen["straddle"] == cen["over256"] == 0 and cen["widest"] <= 32, cen
+    assert cen["narrow_straddle"] == {"ref_c3_lagged": 4, "ref_c5_perm": 1}.get(name, 0), cen
+    # (their few-row ops that happen to lie across slot 256 k are counted apart: cen["narrow_straddle"]; they reach
+    # the find pass's latch in two blocks, never a second trip of the visit loop.) A final dump shows only the
+    # removes the minSeq has not passed; the logs show every range op: none is wider than the generator's cap, 16
+    # units, so none touches more than 16 rows (three leaves)
+    assert json.loads(str(z["workload"]))["max_rem_len"] <= 16
+    ops = z["keep_ops"]
+    rng = ops[np.isin(ops["kind"] & 7, (ol.OP_REMOVE, ol.OP_ANNOTATE))]
+    assert len(rng) > 100 and int((rng["pos2"] - rng["pos1"]).max()) <= 16  # units: at most 16 rows, three leaves
+
+
+def test_oracle_matches_reference():
+    z = fixture()
+    for d, c in enumerate(EVERY):
+        assert _oracle_dumps()[d][1] == int(z["digests"][d]), c.name
+    for k, d in enumerate(z["keep"]):
+        assert _oracle_dumps()[int(d)][0] == ref_dump(z, int(d)), NAMES[int(d)]
+
+
+def ref_positions_of(z, name):
+    """the reference's LocalReference.toPosition of a reference case's references, in creation order"""
+    return [int(x) for x in z["ref_pos"][[NAMES[int(d)] for d in z["ref_docs"]].index(name)]]
+
+
+def _host(profile, extras):
+    z = fixture()
+    idx_all, cs_all = fitting(profile, refs=bool(extras.get("rcap")))
+    step = 8 if profile == "tiled" else len(idx_all)  # a tiled replica's image is hundreds of MB: a few at a time
+    for at in range(0, len(idx_all), step):
+        idx, cs = idx_all[at: at + step], cs_all[at: at + step]
+        _, err, st = core_host.replay_batch(rl.batch(cs), caps_tuple(profile_caps(profile)), **extras)
+        assert (err == 0).all(), [(cs[i].name, st.error_op(int(i))) for i in np.nonzero(err)[0]]
+        for k, d in enumerate(idx):
+            assert st.dump(k) == ref_dump(z, d), f"{profile} {extras}: {cs[k].name}"
+            if extras.get("dcap"):
+                n, h, _ = st.deltas(k)
+                assert (n, h) == (int(z["delta_nwords"][d]), int(z["delta_hashes"][d])), f"{profile}: {cs[k].name}"
+            if cs[k].name in rl.REF_NAMES:
+                assert st.ref_positions(k).tolist() == ref_positions_of(z, cs[k].name), f"{profile}: {cs[k].name}"
+        del st
+    return len(idx_all)
+
+
+def dcap_of(z, idx) -> int:
+    """words of delta stream kept per document: the reference's longest stream among the cases, rounded up"""
+    return 1 << int(np.ceil(np.log2(int(z["delta_nwords"][idx].max()) + 1)))
+
+
+@pytest.mark.parametrize("profile", ["small", "matrix", "flat", "tiled"])
+def test_host_core_matches_reference(profile):
+    n = _host(profile, {})
+    # t_settled_2060 is the tiled profile's; the reference cases need rcap > 0
+    assert n == len(CASES) - len(rl.REF_NAMES) - (0 if profile == "tiled" else 1)
+
+
+@pytest.mark.parametrize("profile", ["small", "flat", "tiled"])
+def test_host_core_with_deltas_and_references_matches_reference(profile):
+    """dcap > 0 and rcap > 0: every case's delta stream, and the reference cases (references on rows of three wave
+    blocks of a wide remove): their positions equal the reference's"""
+    z = fixture()
+    n = _host(profile, dict(dcap=dcap_of(z, fitting(profile, refs=True)[0]), rcap=64))
+    assert n == len(CASES) - (0 if profile == "tiled" else 1)
+
+
+def test_the_reference_cases_hold_references_on_removed_rows():
+    """the fixture's answers show the branch: the SlideOnRemove references of the removed rows slid to the first row
+    after the range's start, the simple ones report no position, the reference outside the range kept its own"""
+    z = fixture()
+    for name in rl.REF_NAMES:
+        pos = ref_positions_of(z, name)
+        assert len(pos) == len(rl.REF_ROWS) == 8 and pos[-1] > 0 and len(set(pos[:-1:2])) == 1, (name, pos)
+        assert all(p == -1 for p in pos[1:-1:2]), (name, pos)
+
+
+def test_regen_count_is_the_host_core_s():
+    """lg_regen's ack has range_logs.REGEN_OPS member records: the ops the host core's reconnect regenerates (its
+    MT_DELTA_REGEN event), as tests/regen_inject.py counts them"""
+    c = EVERY[NAMES.index("lg_regen")]
+    ops, text, props, kv = c.log.arrays()
+    at = int(np.nonzero((ops["kind"] & 0x90) == 0x90)[0][0])
+    st = core_host.HostStore(1, caps_tuple(profile_caps("flat")), dcap=1 << 14)
+    st.start_collab(0, c.log.local_long_id)
+    assert st.replay(0, ops[:at], text, props, kv) == 0
+    n0 = st.deltas(0)[0]
+    assert st.replay(0, ops[at: at + 1], text, props, kv) == 0
+    ev = ol.decode_deltas(st.deltas(0)[2][n0:])
+    assert len(ev) == 1 and ev[0][0] == 3 and len(ev[0][2]) == rl.REGEN_OPS == int((ops["client"][at + 1:] == rl.LOCAL).sum())
+
+
+def test_the_delta_streams_hold_wide_events():
+    """a REMOVE event over at least 300 segments and an ANNOTATE event with property deltas over at least 100, in
+    the host core's stream whose word count and hash are the reference's"""
+    z = fixture()
+    for name, op, least in (("w_whole_rem", 1, 300), ("w_whole_ann", 2, 300), ("w_blocks3_ann", 2, 100)):
+        d = NAMES.index(name)
+        _, err, st = core_host.replay_batch(rl.batch([EVERY[d]]), caps_tuple(profile_caps("flat")),
+                                            dcap=dcap_of(z, [d]))
+        n, h, words = st.deltas(0)
+        assert err[0] == 0 and (n, h) == (int(z["delta_nwords"][d]), int(z["delta_hashes"][d])), name
+        ev = [e for e in ol.decode_deltas(words) if e[0] == op]
+        assert max(len(e[2]) for e in ev) >= least, name
+        if op == 2:
+            assert all(s[3] for e in ev for s in e[2]), "every annotated segment carries property deltas"
+
+
+def test_snapshot_emit_matches_reference():
+    from test_snapshot_ref import long_name, sha
+    z = fixture()
+    for d, c in enumerate(EVERY):
+        tree = sn.emit_from_dump(ref_dump(z, d), c.log.interner, long_name)
+        assert sha(tree) == str(z["snap_sha256"][d]), c.name
+
+
+def cap_profiles(c):
+    """the host profiles a cap case is replayed under: the one it starts in and every one it can be promoted to"""
+    return ["tiled"] if c.profiles == rl.TILED else ["small", "flat", "tiled"]
+
+
+def cap_outcome(c, err, err_op, digest, ref_digest) -> str:
+    """exactly two outcomes are accepted: the reference's digest, or MT_E_CAPACITY at the record that needs the room"""
+    if err == 0 and digest == ref_digest:
+        return "digest"
+    assert (err, err_op) == (MT_E_CAPACITY, c.cut), (c.name, "neither the reference's digest nor MT_E_CAPACITY at "
+                                                     f"record {c.cut}", err, err_op)
+    return "capacity"
+
+
+@pytest.mark.parametrize("name", rl.CAP_NAMES)
+def test_cap_cases_on_the_host_core(name):
+    z = fixture()
+    d = NAMES.index(name)
+    c = EVERY[d]
+    got = {}
+    for profile in cap_profiles(c):
+        dig, err, st = core_host.replay_batch(rl.batch([c]), caps_tuple(profile_caps(profile)))
+        got[profile] = cap_outcome(c, int(err[0]), st.error_op(0), int(dig[0]), int(z["digests"][d]))
+        del st
+    print(name, got)
+    if CAP_OUTCOME[name] == "capacity":
+        assert set(got.values()) == {"capacity"}, got
+    else:  # the host core does not promote: the profile that is too small latches, the larger ones end equal
+        assert got[cap_profiles(c)[-1]] == "digest" and got["flat"] == "digest", got
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------
+def _engine(cs, profile, variant, **extra):
+    from fluidframework_amd.engine import Engine
+    b = rl.batch(cs)
+    eng = Engine(b.ndocs, **variant, **dict(profile_caps(profile), **extra))
+    eng.start_collab(b.local_long_id)
+    return eng, b
+
+
+def _promoted(build_id, cs):
+    want = set().union(*[v for k, v in PROMOTED.items() if build_id.startswith(k)])
+    return [k for k, c in enumerate(cs) if c.name in want]
+
+
+# MT_OPF_REGEN and MT_OP_REF records replay in the client-feature build only (dcap or rcap > 0; mt_oplog.h)
+FEATURE = {"lg_regen"} | set(rl.REF_NAMES)
+
+
+def _gpu_cases(build_id, profile, perm_only, with_promotion, feature=False):
+    """the cases of a GPU batch: every fitting case, and cap_group_small (stated outcome: equal to the reference,
+    after promotion where the build is too small). A document is promoted only by a fresh replay that holds its whole
+    history, in an engine without client features (include/mt_engine.h mt_engine_sync), so the documents THIS build
+    must promote are left out of its delta-stream and two-submit batches; the other builds keep them."""
+    extra = [c for c in CAPS if c.name == "cap_group_small"] if not perm_only else []
+    idx, cs = fitting(profile, perm_only, CASES + extra, refs=feature)
+    mine = set().union(*[v for k, v in PROMOTED.items() if build_id.startswith(k)])
+    drop = (set() if with_promotion else mine) | (set() if feature else FEATURE)
+    keep = [k for k, c in enumerate(cs) if c.name not in drop]
+    return [idx[k] for k in keep], [cs[k] for k in keep]
+
+
+def _local_text(hdr, segs):
+    return "".join(s["text"] for s in segs if s["removedSeq"] is None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", BUILDS, ids=BUILD_IDS)
+def test_gpu_matches_reference(build):
+    name, profile, variant, perm_only = build
+    z = fixture()
+    idx, cs = _gpu_cases(name, profile, perm_only, True)
+    eng, b = _engine(cs, profile, variant)
+    eng.replay(b)
+    _check_state(eng, z, idx, cs, name, ref_dump, _promoted(name, cs))
+    for par in (0, 1):  # mt_engine_dumps under both writers
+        eng.set_variant(MT_VAR_DUMPS_PARALLEL, par)
+        got = eng.dumps()
+        for k, d in enumerate(idx):
+            assert got[k] == ref_dump(z, d), f"{name}: dumps writer {par}: {cs[k].name}"
+    # reads at the local perspective after the final replay
+    parsed = [ol.parse_dump(ref_dump(z, d)) for d in idx]
+    n, st = eng.get_lengths()
+    assert (st == 0).all() and [int(x) for x in n] == [h["length"] for h, _ in parsed], name
+    texts, st = eng.get_texts()
+    assert (st == 0).all(), name
+    for k, (h, segs) in enumerate(parsed):
+        if cs[k].kind == "text" and not any(s["kind"] == ol.SEG_MARKER for s in segs):
+            assert texts[k] == _local_text(h, segs), f"{name}: text of {cs[k].name}"
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", BUILDS, ids=BUILD_IDS)
+def test_gpu_delta_stream_matches_reference(build):
+    name, profile, variant, perm_only = build
+    z = fixture()
+    """dcap > 0 and rcap > 0: the client-feature build, with the reconnect and the local-reference cases"""
+    idx, cs = _gpu_cases(name, profile, perm_only, False, feature=True)
+    eng, b = _engine(cs, profile, variant, dcap=dcap_of(z, idx), rcap=64)
+    eng.replay(b)
+    _check_state(eng, z, idx, cs, name, ref_dump)
+    nref, pos = eng.ref_positions()
+    for k, c in enumerate(cs):
+        want = ref_positions_of(z, c.name) if c.name in rl.REF_NAMES else []
+        assert pos[k, : nref[k]].tolist() == want, f"{name}: reference positions of {c.name}"
+    assert perm_only or sum(c.name in rl.REF_NAMES for c in cs) == 2
+    n, h = eng.delta_state()
+    bad = np.nonzero((n != z["delta_nwords"][idx]) | (h != z["delta_hashes"][idx]))[0]
+    assert len(bad) == 0, f"{name}: delta stream differs from the reference on {[cs[i].name for i in bad]}"
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", BUILDS, ids=BUILD_IDS)
+def test_gpu_two_submits_match_reference(build):
+    """the batch in two parts, cut before each document's first wide op (an ack case: between the local op and its
+    ack): state persists between submits"""
+    name, profile, variant, perm_only = build
+    z = fixture()
+    idx, cs = _gpu_cases(name, profile, perm_only, False)
+    eng, _ = _engine(cs, profile, variant)
+    head, tail = rl.split_at_cut(cs)
+    eng.replay(head)
+    err, _ = eng.errors()
+    assert (err == 0).all()
+    eng.replay(tail)
+    _check_state(eng, z, idx, cs, name + " in two submits", ref_dump)
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", [b for b in BUILDS if not b[3]], ids=[b[0] for b in BUILDS if not b[3]])
+def test_gpu_cap_cases(build):
+    """the cap cases give the outcome they give on the host core, in every build they fit (the matrix build
+    replays PermutationSegment documents only: none of them is one)"""
+    name, profile, variant, perm_only = build
+    z = fixture()
+    idx, cs = fitting(profile, False, CAPS)
+    eng, b = _engine(cs, profile, variant)
+    eng.replay(b)
+    err, err_op = eng.errors()
+    dig = eng.digests()
+    for k, d in enumerate(idx):
+        got = cap_outcome(cs[k], int(err[k]), int(err_op[k]), int(dig[k]), int(z["digests"][d]))
+        print(name, cs[k].name, got)
+        assert got == CAP_OUTCOME[cs[k].name], (name, cs[k].name)
+    eng.close()

@@ -409,6 +409,59 @@ def make_zamboni(node: str) -> None:
           f"{int((odig == digests).sum())}/{b.ndocs} digests; {len(load_msgs)} summaries do not load", flush=True)
 
 
+RANGE_KEEP_ROWS = 100  # cases with fewer rows keep their whole dump in refranges.npz
+
+
+def make_ranges(node: str) -> None:
+    """tests/golden/refranges.npz: the hand-built wide range edits (tests/range_logs.py: removes and annotates over
+    many leaves, perspective mixes, wide local groups and their acks, the drain afterwards, the cap cases) replayed by
+    the reference: per document its digest, the word count and FNV-1a-64 of its delta stream, the SHA-256 of its
+    SnapshotV1 summary at the end of the log, the whole dump of the documents that end with fewer than
+    RANGE_KEEP_ROWS rows, and the positions of the reference cases' local references. Every case's witness must hold
+    on the reference's dump."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_client as oc
+    import range_logs as rl
+    cs = rl.cases() + rl.caps()
+    b = rl.batch(cs)
+    it = cs[0].log.interner
+    cuts = [int(n) for n in np.diff(b.op_off)]  # summarized at the end of the log
+    d = os.path.join(SCRATCH, "ranges")
+    dumps, info, secs, (trees, loaded, tail_err, tail_msgs, load_err, load_msgs) = run_reference(
+        b, d, node, cuts, interner=it, extra=("--deltas",))
+    parsed = [ol.parse_dump(x) for x in dumps]
+    for c, p in zip(cs, parsed):
+        if not c.witness(*p):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+    words = np.fromfile(os.path.join(d, "ref_deltas.bin"), "<i4")
+    woff = np.fromfile(os.path.join(d, "ref_delta_off.bin"), "<i8")
+    per = [words[woff[i]: woff[i + 1]] for i in range(b.ndocs)]
+    digests = np.asarray([fnv1a64(x) for x in dumps], np.uint64)
+    _, odig, oerr = oc.replay_batch(b)
+    if not ((odig == digests).all() and (oerr == 0).all()):
+        raise RuntimeError(f"the oracle differs from the reference on {[c.name for c, a, r in zip(cs, odig, digests) if a != r]}")
+    keep = [i for i, p in enumerate(parsed) if p[0]["nsegs"] < RANGE_KEEP_ROWS]
+    # LocalReference.toPosition of every local reference of the reference cases (-1: detached), in creation order
+    rp = json.load(open(os.path.join(d, "ref_refpos.json")))
+    ref_docs = [i for i, c in enumerate(cs) if c.name in rl.REF_NAMES]
+    if sorted(int(k) for k in rp) != ref_docs or any(len(rp[str(i)]) != len(rl.REF_ROWS) for i in ref_docs):
+        raise RuntimeError(f"local references: expected {len(rl.REF_ROWS)} in documents {ref_docs}, got {rp}")
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refranges.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=digests, nrows=np.asarray([p[0]["nsegs"] for p in parsed], np.int64),
+        ref_docs=np.asarray(ref_docs, np.int64), ref_pos=np.asarray([rp[str(i)] for i in ref_docs], np.int32),
+        keep=np.asarray(keep, np.int64), dumps=np.frombuffer(b"".join(dumps[i] for i in keep), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(dumps[i]) for i in keep])]).astype(np.int64),
+        delta_nwords=np.diff(woff).astype(np.int64), delta_hashes=np.asarray([words_fnv(x) for x in per], np.uint64),
+        snap_sha256=np.asarray([hashlib.sha256(canonical_tree(t).encode()).hexdigest() for t in trees]),
+        source=("packages/dds/merge-tree/src + sequence sharedSequence.ts SubSequence + matrix permutationvector.ts "
+                "(reference, type-erased by tools/ts_erase.py) under node by tools/ref_replay.mjs --deltas with "
+                "snapshots.json; logs: tests/range_logs.py"))
+    cen = rl.census(parsed, it.values)
+    print(f"refranges: {b.ndocs} docs, {b.nops} records, every witness holds, the oracle agrees on every digest; "
+          f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
+
+
 def make_refentry(node: str) -> None:
     """tests/golden/refentry_kat.npz: the refsByOffset-entry KATs (tests/refs_entry_logs.py) replayed by the
     reference: LocalReference.toPosition() of every reference (-2: addLocalReference threw) and the digests."""
@@ -1084,6 +1137,7 @@ def main() -> None:
     ap.add_argument("--replaytool", action="store_true", help="write the client replay tool fixture only")
     ap.add_argument("--subseq", action="store_true", help="write the SubSequence fixtures (refsubseq_*.npz) only")
     ap.add_argument("--zamboni", action="store_true", help="write the zamboni edge-case fixture (refzamboni.npz) only")
+    ap.add_argument("--ranges", action="store_true", help="write the wide range-edit fixture (refranges.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ts_erase.py"), "--out", ERASED], check=True)
@@ -1092,6 +1146,9 @@ def main() -> None:
         return
     if args.zamboni:
         make_zamboni(args.node)
+        return
+    if args.ranges:
+        make_ranges(args.node)
         return
     if args.subseq:
         make_subseq(args.node)

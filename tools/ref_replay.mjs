@@ -196,7 +196,7 @@ function applyRange(client, doc, from, to) {
                 w.push(o.pos1, len, o.type);
             }
             w.push(END, ops.length);
-            if (deltaWords[curDoc]) deltaWords[curDoc].push(...w);
+            if (recording && deltaWords[curDoc]) deltaWords[curDoc].push(...w);
             (regenWords[curDoc] = regenWords[curDoc] || []).push(...w);
             if (ops.length) {
                 const groups = client.peekPendingSegmentGroups(ops.length);
@@ -369,6 +369,7 @@ function hookDeltas(client, words) {
     };
 }
 const deltaWords = [];
+let recording = false; // the replay under way is the one whose delta stream is recorded (not a snapshot's replay)
 // legacy summaries: SharedString's messagesSinceMSNChange of the replica being replayed (null: not kept),
 // and the ops createOpsFromDelta makes of the sequenceDelta events of the message being rebased
 let stash = null;
@@ -419,6 +420,7 @@ function replayDoc(doc, to = opOff[doc + 1], deltas = false) {
     curRefs = [];
     pendingOps = [];
     curDoc = doc;
+    recording = deltas;
     if (deltas) {
         const words = [];
         deltaWords[doc] = words;
