@@ -247,6 +247,7 @@ def replay(log: Log, device: int = 0, **caps):
     c.update(caps)
     eng = Engine(st.batch.ndocs, device=device, **c)  # no start_collab: each replica's COLLAB record starts it
     try:
+        eng.set_value_kinds(ol.value_kinds(st.interner))  # what an incr annotate makes of each recorded value
         eng.replay(st.batch)
         err, err_op = eng.errors()
         bad = [i for i in range(st.batch.ndocs) if err[i]]

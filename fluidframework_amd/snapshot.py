@@ -62,6 +62,15 @@ def _json_spec(seg, props, interner: Optional[ol.Interner] = None):
     return [seg["len"], seg.get("start", UNALLOCATED)]
 
 
+def _match_props(a, b) -> bool:
+    """matchProperties (properties.ts:61-92) of two parsed dump rows, on their raw (key id, value) pairs: NaN never
+    equals itself and a consensus object's `value` is undefined, so a pair holding either never matches (the engine's
+    pv_unmatchable); their JSON forms (null, {"seq": s}) would compare equal."""
+    if (a["flags"] ^ b["flags"]) & ol.DF_HAS_PROPS or a["props"] != b["props"]:
+        return False
+    return not any(isinstance(v, ol.Derived) and v.kind in ("nan", "cons") for _, v in a["props"])
+
+
 def _can_append(a, b) -> bool:
     if a["kind"] == ol.SEG_PERM or b["kind"] == ol.SEG_PERM:  # PermutationSegment.canAppend (87-93)
         if a["kind"] != b["kind"]:
@@ -102,7 +111,7 @@ def extract_segments(hdr, segs, interner: ol.Interner, long_name) -> List[tuple]
             cur = dict(s, _props=props)
             if prev is None:
                 prev = cur
-            elif _can_append(prev, cur) and prev["_props"] == cur["_props"]:
+            elif _can_append(prev, cur) and _match_props(prev, cur):
                 prev = _appended(prev, cur)
             else:
                 push(prev)
@@ -175,7 +184,7 @@ def extract_segments_legacy(hdr, segs, interner: ol.Interner) -> List[tuple]:
         if rs is not None and rs != -1 and rs <= min_seq:
             continue
         cur = dict(s, _props=_props(s, interner))
-        if prev is not None and _can_append(prev, cur) and prev["_props"] == cur["_props"]:
+        if prev is not None and _can_append(prev, cur) and _match_props(prev, cur):
             prev = _appended(prev, cur)
         else:
             if prev is not None:

@@ -175,3 +175,40 @@ def test_gpu_sequence_replicas_match_reference_tool():
         for (p, c, t, n, items), tl, ln, ni, f in zip(reps, z["text_len"][m], z["length"][m], z["nitems"][m],
                                                        z["items_fnv"][m]):
             assert (len(t), n) == (tl, ln) and _items_fnv(items) == (ni, int(f)), (k, p, c)
+
+
+def incr_document():
+    """documents()[1] with two more messages: client c1 sets a string property on [0, 5), then client c2 sends an incr
+    annotate over it (Properties.combine: the string with "undefined" appended)"""
+    _, docs = load()
+    msgs = json.loads(json.dumps(docs[1]))
+    for k, (client, contents) in enumerate((("c1", {"pos1": 0, "pos2": 5, "props": {"client": "Z"}, "type": 2}),
+                                            ("c2", {"pos1": 0, "pos2": 5, "props": {"client": 1}, "type": 2,
+                                                    "combiningOp": {"name": "incr"}}))):
+        m = json.loads(json.dumps(msgs[-1]))
+        m.update(clientId=client, sequenceNumber=m["sequenceNumber"] + 1, referenceSequenceNumber=2000 + k)
+        m["contents"]["contents"]["contents"]["content"]["contents"] = contents
+        msgs.append(m)
+    return msgs
+
+
+def test_host_core_incr_over_a_string_needs_the_value_kinds():
+    """what replay() must declare: without the value kinds the recorded incr latches MT_E_UNSUPPORTED on every
+    replica"""
+    from fluidframework_amd import oplog as ol
+    st = rt.streams(rt.parse(incr_document()))
+    caps = (CAPS["ncap"], CAPS["hcap"], CAPS["acap"], CAPS["mcap"], CAPS["gcap"], CAPS["ccap"])
+    for kinds, want in ((None, 4), (ol.value_kinds(st.interner), 0)):
+        hs = core_host.HostStore(st.batch.ndocs, caps)
+        if kinds is not None:
+            hs.set_value_kinds(kinds)
+        err = [hs.replay(d, *st.batch.doc(d)) for d in range(st.batch.ndocs)]
+        assert err == [want] * st.batch.ndocs, (kinds is None, err)
+
+
+@pytest.mark.gpu
+def test_gpu_replay_declares_value_kinds():
+    """replay_tool.replay over a recorded log with an incr over a string: no MT_E_UNSUPPORTED, every replica
+    converges"""
+    reps = rt.replay(rt.parse(incr_document()), **CAPS)
+    assert len(reps) == 8 and len({(t, n) for _, _, t, n, _ in reps}) == 1

@@ -462,6 +462,59 @@ def make_ranges(node: str) -> None:
           f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
 
 
+def make_props(node: str) -> None:
+    """tests/golden/refprops.npz: the hand-built property-manager cases (tests/prop_logs.py: key slots and op widths,
+    pending-key counts, rewrites, combining ops, zamboni over 24 keys, the cap cases) replayed by the reference: per
+    document its digest and whole canonical dump, the SHA-256 of its SnapshotV1 summary at the end of the log and, for
+    every case without combining ops, the words of its delta stream, their count and FNV-1a-64 (the combining cases run
+    without --deltas: the replayer cannot word a derived previous value; their count is -1). Every witness must hold
+    on the reference's dump and stream."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_client as oc
+    import prop_logs as pl
+    cs = pl.cases() + pl.caps()
+    it = cs[0].log.interner
+    parts = {False: [i for i, c in enumerate(cs) if not c.combining], True: [i for i, c in enumerate(cs) if c.combining]}
+    dumps, trees, per = [None] * len(cs), [None] * len(cs), [np.zeros(0, "<i4")] * len(cs)
+    for comb, idx in parts.items():
+        b = pl.batch([cs[i] for i in idx])
+        cuts = [int(n) for n in np.diff(b.op_off)]  # summarized at the end of the log
+        d = os.path.join(SCRATCH, "props_combine" if comb else "props")
+        dd, info, secs, (tt, loaded, tail_err, tail_msgs, load_err, load_msgs) = run_reference(
+            b, d, node, cuts, interner=it, extra=() if comb else ("--deltas",))
+        if not comb:
+            words = np.fromfile(os.path.join(d, "ref_deltas.bin"), "<i4")
+            woff = np.fromfile(os.path.join(d, "ref_delta_off.bin"), "<i8")
+        for k, i in enumerate(idx):
+            dumps[i], trees[i] = dd[k], tt[k]
+            if not comb:
+                per[i] = words[woff[k]: woff[k + 1]]
+    for c, x, w in zip(cs, dumps, per):
+        if not c.witness(*ol.parse_dump(x)):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+        if c.dwitness is not None and not c.dwitness(ol.decode_deltas(w)):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's delta stream")
+    digests = np.asarray([fnv1a64(x) for x in dumps], np.uint64)
+    plain = [i for i in parts[False] if cs[i].name not in pl.CAP_NAMES]
+    _, odig, oerr = oc.replay_batch(pl.batch([cs[i] for i in plain]))
+    agree = int((odig == digests[plain]).sum())
+    b = pl.batch(cs)
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refprops.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=digests, dumps=np.frombuffer(b"".join(dumps), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(x) for x in dumps])]).astype(np.int64),
+        delta_nwords=np.asarray([-1 if c.combining else len(w) for c, w in zip(cs, per)], np.int64),
+        delta_hashes=np.asarray([words_fnv(x) for x in per], np.uint64),
+        delta_words=np.concatenate(per).astype(np.int32),
+        delta_off=np.concatenate([[0], np.cumsum([len(w) for w in per])]).astype(np.int64),
+        snap_sha256=np.asarray([hashlib.sha256(canonical_tree(t).encode()).hexdigest() for t in trees]),
+        source=("packages/dds/merge-tree/src + sequence sharedSequence.ts SubSequence + matrix permutationvector.ts "
+                "(reference, type-erased by tools/ts_erase.py) under node by tools/ref_replay.mjs --deltas with "
+                "snapshots.json; logs: tests/prop_logs.py"))
+    print(f"refprops: {b.ndocs} docs, {b.nops} records, every witness holds; the oracle agrees on {agree}/{len(plain)} "
+          f"digests of the cases without combining ops; census {pl.census(b)}", flush=True)
+
+
 def make_refentry(node: str) -> None:
     """tests/golden/refentry_kat.npz: the refsByOffset-entry KATs (tests/refs_entry_logs.py) replayed by the
     reference: LocalReference.toPosition() of every reference (-2: addLocalReference threw) and the digests."""
@@ -1138,6 +1191,7 @@ def main() -> None:
     ap.add_argument("--subseq", action="store_true", help="write the SubSequence fixtures (refsubseq_*.npz) only")
     ap.add_argument("--zamboni", action="store_true", help="write the zamboni edge-case fixture (refzamboni.npz) only")
     ap.add_argument("--ranges", action="store_true", help="write the wide range-edit fixture (refranges.npz) only")
+    ap.add_argument("--props", action="store_true", help="write the property-manager fixture (refprops.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ts_erase.py"), "--out", ERASED], check=True)
@@ -1149,6 +1203,9 @@ def main() -> None:
         return
     if args.ranges:
         make_ranges(args.node)
+        return
+    if args.props:
+        make_props(args.node)
         return
     if args.subseq:
         make_subseq(args.node)
