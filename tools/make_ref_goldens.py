@@ -462,6 +462,50 @@ def make_ranges(node: str) -> None:
           f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
 
 
+def make_inserts(node: str) -> None:
+    """tests/golden/refinserts.npz: the hand-built insert cases (tests/insert_logs.py: tie walks over tombstones and
+    pending rows, search alignment on 256-slot boundaries, row splits by offset, child index and child count, node
+    splits, long texts, the cap cases) replayed by the reference: per document its digest, its row count, the word
+    count and FNV-1a-64 of its delta / maintenance stream (INSERT positions, SPLIT events), the SHA-256 of its
+    SnapshotV1 summary at the end of the log and the whole dump of the documents that end with fewer than
+    RANGE_KEEP_ROWS rows. Every case's witness must hold on the reference's dump."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import insert_logs as il
+    import oracle_client as oc
+    cs = il.cases() + il.caps()
+    b = il.batch(cs)
+    it = cs[0].log.interner
+    cuts = [int(n) for n in np.diff(b.op_off)]  # summarized at the end of the log
+    d = os.path.join(SCRATCH, "inserts")
+    dumps, info, secs, (trees, loaded, tail_err, tail_msgs, load_err, load_msgs) = run_reference(
+        b, d, node, cuts, interner=it, extra=("--deltas",))
+    parsed = [ol.parse_dump(x) for x in dumps]
+    for c, p in zip(cs, parsed):
+        if not c.witness(*p):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+    words = np.fromfile(os.path.join(d, "ref_deltas.bin"), "<i4")
+    woff = np.fromfile(os.path.join(d, "ref_delta_off.bin"), "<i8")
+    per = [words[woff[i]: woff[i + 1]] for i in range(b.ndocs)]
+    digests = np.asarray([fnv1a64(x) for x in dumps], np.uint64)
+    _, odig, oerr = oc.replay_batch(b)
+    if not ((odig == digests).all() and (oerr == 0).all()):
+        raise RuntimeError(f"the oracle differs from the reference on {[c.name for c, a, r in zip(cs, odig, digests) if a != r]}")
+    keep = [i for i, p in enumerate(parsed) if p[0]["nsegs"] < RANGE_KEEP_ROWS]
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refinserts.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=digests, nrows=np.asarray([p[0]["nsegs"] for p in parsed], np.int64),
+        keep=np.asarray(keep, np.int64), dumps=np.frombuffer(b"".join(dumps[i] for i in keep), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(dumps[i]) for i in keep])]).astype(np.int64),
+        delta_nwords=np.diff(woff).astype(np.int64), delta_hashes=np.asarray([words_fnv(x) for x in per], np.uint64),
+        snap_sha256=np.asarray([hashlib.sha256(canonical_tree(t).encode()).hexdigest() for t in trees]),
+        source=("packages/dds/merge-tree/src + sequence sharedSequence.ts SubSequence + matrix permutationvector.ts "
+                "(reference, type-erased by tools/ts_erase.py) under node by tools/ref_replay.mjs --deltas with "
+                "snapshots.json; logs: tests/insert_logs.py"))
+    cen = il.census(parsed, [b.doc(i)[0] for i in range(b.ndocs)])
+    print(f"refinserts: {b.ndocs} docs, {b.nops} records, every witness holds, the oracle agrees on every digest; "
+          f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
+
+
 def make_props(node: str) -> None:
     """tests/golden/refprops.npz: the hand-built property-manager cases (tests/prop_logs.py: key slots and op widths,
     pending-key counts, rewrites, combining ops, zamboni over 24 keys, the cap cases) replayed by the reference: per
@@ -1191,6 +1235,7 @@ def main() -> None:
     ap.add_argument("--subseq", action="store_true", help="write the SubSequence fixtures (refsubseq_*.npz) only")
     ap.add_argument("--zamboni", action="store_true", help="write the zamboni edge-case fixture (refzamboni.npz) only")
     ap.add_argument("--ranges", action="store_true", help="write the wide range-edit fixture (refranges.npz) only")
+    ap.add_argument("--inserts", action="store_true", help="write the insert placement / split fixture (refinserts.npz) only")
     ap.add_argument("--props", action="store_true", help="write the property-manager fixture (refprops.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
@@ -1203,6 +1248,9 @@ def main() -> None:
         return
     if args.ranges:
         make_ranges(args.node)
+        return
+    if args.inserts:
+        make_inserts(args.node)
         return
     if args.props:
         make_props(args.node)
