@@ -6569,6 +6569,269 @@ struct Replica {
             return n;
         }
     }
+    /* ---- summary dump (include/mt_oplog.h; the batched read mt_kernels.h k_summary_sizes / k_summaries) ----
+     * SnapshotV1.extractSync (snapshotV1.ts:156-234) / SnapshotLegacy.extractSync (snapshotlegacy.ts:179-242) over
+     * the rows in walk order. Only reads the document (ends_nl would cache RF_NLK in the image: the last unit is
+     * read here instead), so it is reachable from the read kernels alone. */
+    enum { SM_ELIDE = 0, SM_MEMBER = 1, SM_WINDOW = 2 };
+    /* what extraction does with the row in slot s: drops it, lets it join or start a settled run, or (v1) emits
+     * it with its merge info, which closes the open run */
+    MT_HD int32_t sum_class(int32_t s, int32_t mode) {
+        const int32_t seq = z.seq(s), rs = z.rseq(s), ms = h.minSeq;
+        const bool rem = rs != NOREM;
+        if (mode == MT_SUMMARY_LEGACY) {
+            if (z.len(s) <= 0 || seq == UNASSIGNED_SEQ || seq > ms) return SM_ELIDE;
+            return rem && rs != UNASSIGNED_SEQ && rs <= ms ? SM_ELIDE : SM_MEMBER;
+        }
+        if (seq == UNASSIGNED_SEQ || (rem && rs <= ms)) return SM_ELIDE; /* a pending removal (-1) is elided too */
+        return seq <= ms && !rem ? SM_MEMBER : SM_WINDOW;
+    }
+    /* canAppend && matchProperties of run member a and the next member b, without canAppend's length rule (which
+     * tests the grown run): kinds, a's last unit, the handle rule. A PermutationSegment run's start + grown length
+     * is its last member's start + length, so the handle rule is the pair's. match_props (shared with zamboni, which
+     * this does not change) tests the RF_PROPS bits first; its MT_PROF_SCOPE is a no-op here: the read kernels leave
+     * `prof` null. */
+    MT_HD bool sum_pair(int32_t a, int32_t b) {
+        const int32_t fa = z.flags(a), fb = z.flags(b);
+        if ((fa | fb) & RF_PERM) {
+            if (!(fa & fb & RF_PERM) || !perm_follows(a, b, z.len(a))) return false;
+        } else {
+            if ((fa | fb) & RF_MARKER) return false;
+            const int32_t La = z.len(a);
+            if (La > 0 && !run_doc() && arena_base(zh->arenaSide)[cold(a).toff + La - 1] == '\n') return false;
+        }
+        return match_props(a, b);
+    }
+    /* canAppend's length rule has no part in a PermutationSegment's (permutationvector.ts:87-93) */
+    MT_HD bool sum_long(int32_t fl, int32_t L, int32_t G) const { return L > G && !(fl & RF_PERM); }
+    /* The record of row s without its text, at c (2-byte aligned; NULL: nothing is written): the row's own record
+     * (`window`) or that of a settled run of `len` units that s starts. Returns its size,
+     * 40 + 4 nprops + 8 nderived + 4 for a handle. */
+    MT_HD int32_t sum_fixed(uint8_t* c, int32_t s, bool window, int32_t len) {
+        const uint8_t fl = z.flags(s);
+        const typename HT::Cold& cs = cold(s);
+        const bool dv = (zh->ndv & 0xFFFF) != 0;
+        int32_t np = 0, nd = 0;
+        if (fl & RF_PROPS)
+            for (int q = 0; q < HT::K; q++) {
+                const int32_t v = cs.pv[q];
+                if (v) np++;
+                if (dv && v >= MT_VALUE_DERIVED && v < MT_VALUE_NAN) nd++;
+            }
+        const bool hnd = (fl & RF_PERM) && cs.toff != 0;
+        const int32_t fixed = 40 + 4 * np + 8 * nd + (hnd ? 4 : 0);
+        if (!c) return fixed;
+        const bool rem = window && z.rseq(s) != NOREM;
+        const uint32_t kind = (fl & RF_MARKER) ? MT_SEG_MARKER : (fl & RF_PERM) ? MT_SEG_PERM : run_doc() ? MT_SEG_RUN : MT_SEG_TEXT;
+        const uint32_t df = ((fl & RF_PROPS) ? MT_DF_HAS_PROPS : 0) | (rem ? MT_DF_REMOVED : 0) | (hnd ? MT_DF_HANDLE : 0);
+        put32(c, kind | (df << 8));
+        put32(c + 4, (uint32_t)len);
+        put32(c + 8, window ? (uint32_t)z.seq(s) : 0);
+        put32(c + 12, window ? (uint32_t)long_of_cli(s) : (uint32_t)-1);
+        put32(c + 16, rem ? (uint32_t)z.rseq(s) : 0);
+        put32(c + 20, rem ? (uint32_t)long_of_rcli(s) : 0);
+        put32(c + 24, 0);
+        put32(c + 28, 0);
+        put32(c + 32, 0);
+        put32(c + 36, (uint32_t)np | ((fl & RF_MARKER) ? (uint32_t)(cs.toff & 0xFFFF) << 16 : 0));
+        c += 40;
+        uint8_t* cd = c + 4 * np; /* the derived values' contents follow the pairs, in pair order */
+        int32_t last = -1;
+        for (int q = 0; q < np; q++) { /* props sorted by global key id */
+            int32_t best = -1, bk = 0x7fffffff;
+            for (int k = 0; k < HT::K; k++) {
+                const int32_t key = keys[k];
+                if (cs.pv[k] && key > last && key < bk) {
+                    bk = key;
+                    best = k;
+                }
+            }
+            last = bk;
+            uint32_t v = cs.pv[best];
+            if (v >= MT_VALUE_DERIVED && v < MT_VALUE_NAN) {
+                if (dv) {
+                    uint32_t a0, a1 = 0;
+                    if (v < MT_VALUE_CONS0) {
+                        const int32_t x = z.dvs[v - MT_VALUE_STRCAT0];
+                        a0 = (uint32_t)x & 0xFFFF, a1 = (uint32_t)x >> 16;
+                    } else {
+                        a0 = (uint32_t)z.dvc[v - MT_VALUE_CONS0];
+                    }
+                    put32(cd, a0);
+                    put32(cd + 4, a1);
+                    cd += 8;
+                }
+                v = v < MT_VALUE_CONS0 ? MT_VALUE_STRCAT0 : MT_VALUE_CONS0;
+            }
+            put32(c, (uint32_t)bk | (v << 16));
+            c += 4;
+        }
+        if (hnd) put32(cd, (uint32_t)cs.toff);
+        return fixed;
+    }
+    /* Serial summary dump (only lane 0 writes the buffer); returns the byte count. out == NULL only sizes. Nothing
+     * is written past cap, and the header only when the whole summary fits. The open run's record is the last
+     * thing written, so a member's text goes to the end and the run's len field is patched as it grows. */
+    MT_HD int64_t summary(uint8_t* out, int64_t cap, int32_t mode) {
+        uint8_t* o = w.lane() == 0 ? out : nullptr;
+        const uint16_t* base = arena_base(zh->arenaSide);
+        const int32_t G = run_doc() ? MT_RUN_MAXRUN : GRANULARITY;
+        int64_t n = 24, lenOff = 0;
+        int32_t nsegs = 0, R = 0, last = -1; /* the open run: its grown length and last member (-1: none open) */
+        for (int32_t k = 0; kvalid(k); k = knext(k)) {
+            const int32_t lf = leaf_at(k), lc = nch[lf];
+            for (int32_t jj = 0; jj < lc; jj++) {
+                const int32_t s = lf * MAXN + jj, cls = sum_class(s, mode);
+                if (cls == SM_ELIDE) continue; /* does not close the run */
+                const int32_t fl = z.flags(s), L = z.len(s);
+                if (cls == SM_MEMBER && last >= 0 && sum_pair(last, s) && !(sum_long(fl, L, G) && R > G)) {
+                    R += L;
+                    if (o && lenOff + 4 <= cap) put32(o + lenOff, (uint32_t)R);
+                } else {
+                    const int32_t fixed = sum_fixed(nullptr, s, false, 0);
+                    if (o && n + fixed <= cap) sum_fixed(o + n, s, cls == SM_WINDOW, L);
+                    lenOff = n + 4;
+                    n += fixed;
+                    nsegs++;
+                    R = L;
+                }
+                if (!(fl & RF_NOTEXT)) {
+                    if (o && n + 2 * (int64_t)L <= cap) {
+                        uint16_t* t = (uint16_t*)(o + n);
+                        const uint16_t* src = base + cold(s).toff;
+                        for (int32_t i = 0; i < L; i++) t[i] = src[i];
+                    }
+                    n += 2 * (int64_t)L;
+                }
+                last = cls == SM_MEMBER ? s : -1;
+            }
+        }
+        if (o && n <= cap) {
+            const int32_t hdr[6] = {h.currentSeq, h.minSeq, zh->localSeq, length_local(), nsegs, 0};
+            for (int i = 0; i < 6; i++) put32(o + 4 * i, (uint32_t)hdr[i]);
+        }
+        return n;
+    }
+    /* The summary dump written by the whole wave: summary()'s bytes and return value. Per pass of 8 leaves x 8 rows
+     * (dump_wave's walk) every lane classifies its row and tests it against the member in front of it (sum_pair;
+     * the first one against the carried run's last member). The length rule, the one serial dependency, has a
+     * closed form: rows that pair form a chain, a short row (<= G) always joins, and a long row starts a new run iff
+     * the run in front of it holds more than G units, i.e. iff an earlier long row exists in the chain (the run
+     * holds it, or was started by a later one) or the chain before it is longer than G (no long row yet: the
+     * run is the whole chain). An open run enters the next pass as a chain prefix of its grown length. Segmented
+     * sums over ballots then give every head its run's length, an exclusive scan places the records, heads and
+     * window rows write their fixed parts and scatter_copy moves every row's text into its run's. The open run is
+     * the last thing written: its later members' texts go to the pass's start and lane 0 patches its len field.
+     * A pass is written only if it ends inside cap, the header only if the whole summary does. Every lane must
+     * call this; the one-lane host build takes the serial path. */
+    MT_HD int64_t summary_wave(uint8_t* out, int64_t cap, int32_t mode) {
+        if constexpr (W::N < MAXN * MAXN) {
+            return summary(out, cap, mode);
+        } else {
+            const int32_t l = w.lane();
+            const uint16_t* base = arena_base(zh->arenaSide);
+            const int32_t G = run_doc() ? MT_RUN_MAXRUN : GRANULARITY;
+            const int32_t llen = out ? length_local() : 0;
+            const uint64_t below = ((uint64_t)1 << l) - 1, upto = below | ((uint64_t)1 << l);
+            int64_t n = 24, lenOff = 0; /* lenOff: the open run's len field */
+            int32_t nsegs = 0, cR = 0, cLast = -1; /* the open run: its grown length and last member (-1: none open) */
+            bool cText = false;                    /* the open run bears text */
+            int32_t k = 0;
+            bool more = kvalid(0);
+            const int32_t li = l >> 3, j = l & (MAXN - 1);
+            /* Of the pass's shuffles, the decisions and the size need psl / pcl, Ech, add, Enh and the carry's (lrh, hR,
+             * hF, cls and s of the last row); Erh / trh (text places) and hO (the len field's place) serve the fill
+             * alone. The sizing kernel runs them too: one decision code for both calls. */
+            while (more) {
+                int32_t leaf = -1;
+                for (int32_t i = 0; i < MAXN && more; i++) {
+                    int32_t lf = leaf_at(k);
+                    if (i == li) leaf = lf;
+                    k = knext(k);
+                    more = kvalid(k);
+                }
+                const int32_t s = leaf >= 0 && j < nch[leaf] ? leaf * MAXN + j : -1;
+                const int32_t cls = s >= 0 ? sum_class(s, mode) : (int32_t)SM_ELIDE;
+                const uint64_t live = w.ballot(cls != SM_ELIDE);
+                if (!live) continue; /* a whole pass elided: the run stays open */
+                const bool mem = cls == SM_MEMBER, win = cls == SM_WINDOW;
+                const int32_t fl = cls != SM_ELIDE ? (int32_t)z.flags(s) : 0, L = cls != SM_ELIDE ? z.len(s) : 0;
+                const bool text = cls != SM_ELIDE && !(fl & RF_NOTEXT);
+                /* the row in front (elided ones skipped): a member of this pass, or the carried run's last */
+                const uint64_t lb = live & below;
+                const int32_t pl = lb ? 63 - __builtin_clzll(lb) : -1;
+                const int32_t psl = w.shfl(s, pl < 0 ? 0 : pl), pcl = w.shfl(cls, pl < 0 ? 0 : pl);
+                const int32_t ps = pl < 0 ? cLast : pcl == SM_MEMBER ? psl : -1;
+                const bool pok = mem && ps >= 0 && sum_pair(ps, s);
+                int32_t tot;
+                const int32_t E = w.excl_scan(mem ? L : 0, &tot); /* member units before the lane */
+                const bool lng = mem && sum_long(fl, L, G);
+                const uint64_t chm = w.ballot(mem && !pok), lgm = w.ballot(lng);
+                /* the chain's head (none: it continues the carried run), its length and long rows before the lane */
+                const uint64_t cb = chm & upto;
+                const int32_t ch = cb ? 63 - __builtin_clzll(cb) : -1;
+                const int32_t Ech = w.shfl(E, ch < 0 ? 0 : ch);
+                const int32_t pre = ch >= 0 ? E - Ech : E + cR;
+                const bool seen = ch >= 0 ? ((lgm & below) >> ch) != 0 : ((lgm & below) != 0 || cR > G);
+                const bool head = mem && (!pok || (lng && (seen || pre > G)));
+                const bool rec = head || win;
+                const uint64_t hm = w.ballot(head);
+                /* members before the first head extend the carried run */
+                const int32_t add = w.shfl(E, hm ? __builtin_ctzll(hm) : 0);
+                const int32_t addU = hm ? add : tot, addT = cText ? 2 * addU : 0;
+                /* a head's run ends at the next head */
+                const uint64_t ha = hm & ~upto;
+                const int32_t Enh = w.shfl(E, ha ? __builtin_ctzll(ha) : 0);
+                const int32_t rl = head ? (ha ? Enh : tot) - E : 0;
+                const int32_t fixed = rec ? sum_fixed(nullptr, s, false, 0) : 0;
+                int32_t ptot;
+                const int32_t eo = w.excl_scan(fixed + (text ? 2 * (head ? rl : win ? L : 0) : 0), &ptot);
+                ptot += addT;
+                nsegs += __builtin_popcountll(w.ballot(rec));
+                /* a member's run head in this pass (none: the carried run) and its text's place in that run's */
+                const uint64_t hb = hm & upto;
+                const int32_t rh = hb ? 63 - __builtin_clzll(hb) : -1;
+                const int32_t Erh = w.shfl(E, rh < 0 ? 0 : rh), trh = w.shfl(addT + eo + fixed, rh < 0 ? 0 : rh);
+                const int32_t tl = text ? L : 0;
+                const int32_t td = win ? addT + eo + fixed : rh >= 0 ? trh + 2 * (E - Erh) : 2 * E;
+                if (out && n + ptot <= cap) { /* wave-uniform */
+                    if (rec) sum_fixed(out + n + addT + eo, s, win, head ? rl : L);
+                    if (addU > 0 && l == 0) put32(out + lenOff, (uint32_t)(cR + addU));
+                    scatter_copy((uint16_t*)(out + n), td >> 1, tl, tl > 0 ? (int32_t)cold(s).toff : 0, base);
+                }
+                /* the run the pass leaves open: that of its last row, if a member */
+                const int32_t ll = 63 - __builtin_clzll(live);
+                const int32_t lrh = w.shfl(rh, ll);
+                const int32_t hR = w.shfl(rl, lrh < 0 ? 0 : lrh), hO = w.shfl(eo, lrh < 0 ? 0 : lrh),
+                              hF = w.shfl(fl, lrh < 0 ? 0 : lrh);
+                if (w.shfl(cls, ll) == SM_MEMBER) {
+                    if (lrh >= 0) {
+                        cR = hR;
+                        lenOff = n + addT + hO + 4;
+                        cText = !(hF & RF_NOTEXT);
+                    } else {
+                        cR += addU;
+                    }
+                    cLast = w.shfl(s, ll);
+                } else {
+                    cLast = -1, cR = 0, cText = false;
+                }
+                n += ptot;
+                w.sync(); /* the next pass may patch a len field this one wrote */
+            }
+            if (out && n <= cap && l < 6) {
+                const int32_t hv = l == 0   ? h.currentSeq
+                                   : l == 1 ? h.minSeq
+                                   : l == 2 ? zh->localSeq
+                                   : l == 3 ? llen
+                                   : l == 4 ? nsegs
+                                            : 0;
+                put32(out + 4 * l, (uint32_t)hv);
+            }
+            w.sync();
+            return n;
+        }
+    }
     MT_HD static uint64_t fnv(const uint8_t* p, int64_t n) {
         uint64_t h = MT_FNV_OFFSET;
         for (int64_t i = 0; i < n; i++) {

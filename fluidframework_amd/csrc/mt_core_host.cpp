@@ -176,6 +176,13 @@ int64_t mth_dump(mth_store* s, int64_t doc, uint8_t* out, int64_t cap) {
     return with_replica(s, doc, [&](auto& r) { return r.dump(out, cap); });
 }
 
+/* the summary dump (mt_oplog.h; mode MT_SUMMARY_*): Replica::summary, what mt_engine_summaries returns per document
+ * (an unknown mode: -16, the engine's -MT_E_ARG) */
+int64_t mth_summary(mth_store* s, int64_t doc, int32_t mode, uint8_t* out, int64_t cap) {
+    if (mode != MT_SUMMARY_V1 && mode != MT_SUMMARY_LEGACY) return -16;
+    return with_replica(s, doc, [&](auto& r) { return r.summary(out, cap, mode); });
+}
+
 uint64_t mth_digest(mth_store* s, int64_t doc) {
     return with_replica(s, doc, [](auto& r) { return r.digest(); });
 }

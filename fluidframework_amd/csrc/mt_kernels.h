@@ -845,6 +845,38 @@ __global__ __launch_bounds__(WG) void k_dumps(Store<HT> st, int64_t m, const Rea
         (void)r.dump(out + o, cap);
 }
 
+/* ---- batched summaries (mt_engine_summaries): the summary dump (mt_oplog.h) of each query's document; as the
+ * batched dumps, only q.doc and q.slot are read ---- */
+#ifndef MT_SUMMARIES_PARALLEL_DEFAULT
+#define MT_SUMMARIES_PARALLEL_DEFAULT true /* k_summaries' writer: Replica::summary_wave or the serial summary */
+#endif
+/* the byte size of query i's summary dump (size[slot]): Replica::summary_wave without a buffer, the decisions of
+ * the fill */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_summary_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int32_t mode,
+                                                     int64_t* size) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int64_t n = r.summary_wave(nullptr, 0, mode);
+    if (threadIdx.x == 0) size[q.slot] = n;
+}
+/* query i's summary dump into out[off[slot], off[slot + 1]) and nowhere else. PAR: the whole wave writes
+ * (Replica::summary_wave); else lane 0 writes (Replica::summary): the same bytes either way. */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_summaries(Store<HT> st, int64_t m, const ReadQ* qs, int32_t mode,
+                                                 const int64_t* off, uint8_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    if constexpr (PAR)
+        (void)r.summary_wave(out + o, cap, mode);
+    else
+        (void)r.summary(out + o, cap, mode);
+}
+
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
  * out[2i+1] = its generation; *n = the segment count (writes at most cap pairs) */
 template <class HT>
@@ -993,6 +1025,7 @@ struct mt_engine {
     std::vector<uint8_t> h_vkind;
     bool texts_packed = MT_TEXTS_PACKED_DEFAULT; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
     bool dumps_parallel = MT_DUMPS_PARALLEL_DEFAULT; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
+    bool summaries_parallel = MT_SUMMARIES_PARALLEL_DEFAULT; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
@@ -1053,6 +1086,9 @@ struct ProfOps {
     int32_t (*dump_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize);
     int32_t (*dumps)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff, uint8_t* dout,
                      bool par);
+    int32_t (*summary_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, int64_t* dsize);
+    int32_t (*summaries)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, const int64_t* doff,
+                         uint8_t* dout, bool par);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1177,8 +1213,24 @@ struct Launch {
             hipLaunchKernelGGL((k_dumps<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
         return launch_check(e, "k_dumps");
     }
+    static int32_t summary_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode,
+                                 int64_t* dsize) {
+        hipLaunchKernelGGL((k_summary_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, mode, dsize);
+        return launch_check(e, "k_summary_sizes");
+    }
+    static int32_t summaries(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode,
+                             const int64_t* doff, uint8_t* dout, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_summaries<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, mode,
+                               doff, dout);
+        else
+            hipLaunchKernelGGL((k_summaries<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, mode,
+                               doff, dout);
+        return launch_check(e, "k_summaries");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
         return ProfOps{init,   start_collab, replay, hdr,     digest,     dump,  length, text,       seg,
-                       refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps};
+                       refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps,
+                       summary_sizes, summaries};
     }
 };

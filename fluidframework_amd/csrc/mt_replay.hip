@@ -870,6 +870,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value != 0 && value != 1) return MT_E_ARG;
         e->dumps_parallel = value == 1;
         return MT_OK;
+    case MT_VAR_SUMMARIES_PARALLEL:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->summaries_parallel = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1254,7 +1258,13 @@ int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const 
     return total;
 }
 
-int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap) {
+extern "C++" {
+/* The sizing contract of the batched dumps and summaries, in one place: plan the queries, size(engine, stream, queries,
+ * count, sizes) per run, the prefix sum on the host into off_out[0..m], then (when `out` is given and the total fits
+ * cap: all or nothing) fill(engine, stream, queries, count, offsets, bytes) per run and one copy back. */
+template <class FS, class FF>
+static int64_t windows_read(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap,
+                            FS&& size, FF&& fill) {
     if (!e || m < 0 || cap < 0) return -MT_E_ARG;
     if (m == 0) return 0;
     if (!off_out) return -MT_E_ARG;
@@ -1272,7 +1282,7 @@ int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* o
     if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
         return -MT_E_HIP;
     rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
-        return x->ops->dump_sizes(x, s, n, q, dsize);
+        return size(x, s, n, q, dsize);
     });
     if (rc) return -rc;
     if (hipMemcpyAsync(off_out + 1, dsize, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
@@ -1286,14 +1296,40 @@ int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* o
     uint8_t* dout = (uint8_t*)e->tmp.p;
     if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
         return -MT_E_HIP;
-    const bool par = e->dumps_parallel;
     rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
-        return x->ops->dumps(x, s, n, q, doff, dout, par);
+        return fill(x, s, n, q, doff, dout);
     });
     if (rc) return -rc;
     if (hipMemcpyAsync(out, dout, (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
     return total;
+}
+}
+
+int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap) {
+    const bool par = e && e->dumps_parallel;
+    return windows_read(
+        e, m, docs, off_out, out, cap,
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, int64_t* dsize) {
+            return x->ops->dump_sizes(x, s, n, q, dsize);
+        },
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, const int64_t* doff, uint8_t* dout) {
+            return x->ops->dumps(x, s, n, q, doff, dout, par);
+        });
+}
+
+int64_t mt_engine_summaries(mt_engine* e, int64_t m, const int64_t* docs, int32_t mode, int64_t* off_out, uint8_t* out,
+                            int64_t cap) {
+    if (mode != MT_SUMMARY_V1 && mode != MT_SUMMARY_LEGACY) return -MT_E_ARG;
+    const bool par = e && e->summaries_parallel;
+    return windows_read(
+        e, m, docs, off_out, out, cap,
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, int64_t* dsize) {
+            return x->ops->summary_sizes(x, s, n, q, mode, dsize);
+        },
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, const int64_t* doff, uint8_t* dout) {
+            return x->ops->summaries(x, s, n, q, mode, doff, dout, par);
+        });
 }
 
 /* k_segs over m queries: res[i * MT_SEGQ_N ..] = query i's words; status_out[i] = MT_E_UNSUPPORTED for a refused one */

@@ -43,6 +43,7 @@ class _Caps(ctypes.Structure):
 _LIB = None
 MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS, MT_VAR_TEXTS_PACKED = 1, 2, 3, 4  # include/mt_engine.h
 MT_VAR_DUMPS_PARALLEL = 5
+MT_VAR_SUMMARIES_PARALLEL = 6
 
 
 def lib() -> ctypes.CDLL:
@@ -112,6 +113,8 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_get_texts.restype = i64
         L.mt_engine_dumps.argtypes = [vp, i64, vp, vp, vp, i64]
         L.mt_engine_dumps.restype = i64
+        L.mt_engine_summaries.argtypes = [vp, i64, vp, i32, vp, vp, i64]
+        L.mt_engine_summaries.restype = i64
         L.mt_engine_get_containing_segments.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_resolve_remote_client_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_adjust_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
@@ -407,6 +410,34 @@ class Engine:
     def dumps(self, docs=None) -> list:
         """The canonical dump of every query's document (mt_engine_dumps): a list of bytes."""
         buf, off = self.dumps_raw(docs)
+        raw = buf.tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    def summaries_raw(self, docs=None, legacy: bool = False):
+        """mt_engine_summaries as arrays: (bytes, off); query i's summary dump (include/mt_oplog.h: the segments
+        SnapshotV1.extractSync yields, or SnapshotLegacy's with `legacy`, extracted on the device) is
+        bytes[off[i]:off[i+1]]. docs None = every document. One size query and one fill."""
+        m, d, _, _ = self._queries(docs, None, None)
+        off = np.zeros(m + 1, np.int64)
+        if not m:
+            return np.zeros(0, np.uint8), off
+        mode = ol.SUMMARY_LEGACY if legacy else ol.SUMMARY_V1
+
+        def call(out, cap):
+            n = self.L.mt_engine_summaries(self.h, m, self._pn(d), mode, _p(off), out, cap)
+            if n < 0:
+                raise EngineError(f"summaries failed {n}", -n)
+            return n
+        n = call(None, 0)
+        buf = np.zeros(max(n, 1), np.uint8)
+        if call(_p(buf), n) != n:
+            raise EngineError("summaries size changed")
+        return buf[:n], off
+
+    def summaries(self, docs=None, legacy: bool = False) -> list:
+        """The summary dump of every query's document (mt_engine_summaries): a list of bytes, each read by
+        oplog.parse_dump and mapped to segment specs by snapshot.specs_from_summary."""
+        buf, off = self.summaries_raw(docs, legacy)
         raw = buf.tobytes()
         return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
 

@@ -118,6 +118,9 @@ export declare class ReplayEngine {
     getTexts(docs?: number[]): string[];
     /** the canonical dump of every listed document (default: all), two launches for the list (mt_engine_dumps) */
     dumps(docs?: number[]): Buffer[];
+    /** the summary dump of every listed document (default: all): the segments SnapshotV1.extractSync (or, with
+     *  legacy, SnapshotLegacy.extractSync) yields, extracted on the device (mt_engine_summaries); decodeDump reads it */
+    summaries(docs?: number[], options?: { legacy?: boolean }): Buffer[];
     longIndex(name: string): number;
 }
 

@@ -405,6 +405,16 @@ class ReplayEngine {
         const { data, offsets } = addon.dumps(this.h, docs);
         return Array.from({ length: offsets.length - 1 }, (_, i) => data.subarray(offsets[i], offsets[i + 1]));
     }
+
+    /* the summary dump (include/mt_oplog.h: the segments SnapshotV1.extractSync yields, or SnapshotLegacy's with
+     * {legacy: true}, filtered, coalesced and concatenated on the device; decodeDump reads it) of every listed
+     * document (all by default) as Buffers over one allocation, from two launches (mt_engine_summaries) */
+    summaries(docs, options) {
+        this.flush();
+        checkDocs(this, docs);
+        const { data, offsets } = addon.summaries(this.h, docs, !!(options && options.legacy));
+        return Array.from({ length: offsets.length - 1 }, (_, i) => data.subarray(offsets[i], offsets[i + 1]));
+    }
 }
 
 /* the latched errors of the listed documents (undefined: all), read in one call */

@@ -680,6 +680,46 @@ static napi_value js_dumps(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* summaries(h[, docs[, legacy]]) -> {data: Buffer, offsets: number[]}: the summary dump (include/mt_oplog.h) of each
+ * listed document (mt_engine_summaries: the segments SnapshotV1.extractSync yields, or SnapshotLegacy's with `legacy`,
+ * extracted on the device; a size query and a fill, two launches); document i's is data[offsets[i], offsets[i + 1]) */
+static napi_value js_summaries(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    size_t argc = 3;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1) {
+        napi_throw_type_error(env, nullptr, "missing arguments");
+        return nullptr;
+    }
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = true, legacy = false;
+    if (!e || (argc > 1 && !docs_of(env, argv[1], &docs, &all))) return nullptr;
+    if (argc > 2) {
+        napi_value b;
+        NAPI_OK(napi_coerce_to_bool(env, argv[2], &b));
+        NAPI_OK(napi_get_value_bool(env, b, &legacy));
+    }
+    const int32_t mode = legacy ? MT_SUMMARY_LEGACY : MT_SUMMARY_V1;
+    const int64_t m = all ? mt_engine_ndocs(e) : (int64_t)docs.size();
+    const int64_t* dp = all ? nullptr : docs.data();
+    std::vector<int64_t> off((size_t)m + 1, 0);
+    int64_t n = mt_engine_summaries(e, m, dp, mode, off.data(), nullptr, 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_summaries");
+    void* data = nullptr;
+    napi_value buf, offs, out;
+    NAPI_OK(napi_create_buffer(env, (size_t)n, &data, &buf));
+    if (n > 0) {
+        int64_t n2 = mt_engine_summaries(e, m, dp, mode, off.data(), (uint8_t*)data, n);
+        if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_summaries");
+    }
+    NAPI_OK(napi_create_array_with_length(env, (size_t)m + 1, &offs));
+    for (int64_t i = 0; i <= m; i++) NAPI_OK(napi_set_element(env, offs, (uint32_t)i, num(env, (double)off[(size_t)i])));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "data", buf));
+    NAPI_OK(napi_set_named_property(env, out, "offsets", offs));
+    return out;
+}
+
 /* adjustPositions(h, docs, pos, fromSeqs, longClients) -> [Int32Array positions (-1: undefined), Int32Array status]:
  * PermutationVector.adjustPosition for a batch of remote ops (mt_engine_adjust_positions); docs is an array of
  * document ids, the others Int32Arrays of its length */
@@ -803,7 +843,7 @@ static napi_value init(napi_env env, napi_value exports) {
                {"dump", js_dump},           {"segmentIds", js_segment_ids},
                {"submitDocs", js_submit_docs}, {"docError", js_doc_error}, {"setValueKinds", js_set_value_kinds},
                {"getLengths", js_get_lengths}, {"getTexts", js_get_texts}, {"adjustPositions", js_adjust_positions},
-               {"dumps", js_dumps}};
+               {"dumps", js_dumps},         {"summaries", js_summaries}};
     for (auto& f : fns) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.cb, nullptr, &fn));

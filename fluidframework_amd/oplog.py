@@ -216,6 +216,7 @@ def value_kinds(interner: "Interner") -> np.ndarray:
 
 # canonical-dump segment flag bits (include/mt_oplog.h MT_DF_*)
 DF_HAS_PROPS, DF_REMOVED, DF_LSEQ, DF_LRSEQ, DF_HANDLE = 1, 2, 4, 8, 16
+SUMMARY_V1, SUMMARY_LEGACY = 0, 1  # MT_SUMMARY_* (mt_oplog.h): the modes of the summary dump
 HANDLE_UNALLOCATED = -0x80000000  # Handle.unallocated (matrix handletable.ts:11)
 
 

@@ -131,10 +131,35 @@ def extract_segments(hdr, segs, interner: ol.Interner, long_name) -> List[tuple]
     return out
 
 
-def emit_v1(hdr, segs, interner: ol.Interner, long_name, chunk_size: int = CHUNK_SIZE) -> dict:
+def specs_from_summary(hdr, segs, interner: ol.Interner, long_name) -> List[tuple]:
+    """The (json spec, length) list of a parsed summary dump (include/mt_oplog.h; Engine.summaries): one per
+    record, nothing merged or dropped here, the extraction was done where the rows are. A record with seq above
+    the MSN or a removal is a window segment and keeps its merge info as extract_segments writes it; the legacy
+    mode emits none, so one mapping serves both."""
+    min_seq = hdr["minSeq"]
+    out: List[tuple] = []
+    for s in segs:
+        spec = _json_spec(s, _props(s, interner), interner)
+        removed = s["removedSeq"] is not None
+        if s["seq"] > min_seq or removed:
+            raw: Dict[str, Any] = {"json": spec}
+            if s["seq"] > min_seq:
+                raw["seq"] = s["seq"]
+                raw["client"] = long_name(s["client"])
+            if removed:
+                raw["removedSeq"] = s["removedSeq"]
+                raw["removedClient"] = long_name(s["removedClient"])
+            spec = raw
+        out.append((spec, s["len"]))
+    return out
+
+
+def emit_v1(hdr, segs, interner: ol.Interner, long_name, chunk_size: int = CHUNK_SIZE, specs=None) -> dict:
     """SnapshotV1.emit (snapshotV1.ts:82-154): the ITree of a merge-tree snapshot (header blob, then
-    body_<i> blobs), contents serialized like serializeAsMaxSupportedVersion with JSON.stringify."""
-    specs = extract_segments(hdr, segs, interner, long_name)
+    body_<i> blobs), contents serialized like serializeAsMaxSupportedVersion with JSON.stringify. `specs`: the
+    extracted segments when the caller has them already (specs_from_summary); `segs` is then unused."""
+    if specs is None:
+        specs = extract_segments(hdr, segs, interner, long_name)
     chunks = []
     start = 0
     while True:
@@ -196,14 +221,16 @@ def extract_segments_legacy(hdr, segs, interner: ol.Interner) -> List[tuple]:
 
 
 def emit_legacy(hdr, segs, interner: ol.Interner, catchup: Optional[List[dict]] = None,
-                chunk_size: int = CHUNK_SIZE, catchup_blob: str = CATCHUP) -> dict:
+                chunk_size: int = CHUNK_SIZE, catchup_blob: str = CATCHUP, specs=None) -> dict:
     """SnapshotLegacy.extractSync + emit (snapshotlegacy.ts:104-242), what Client.snapshot writes unless
     newMergeTreeSnapshotFormat is set (client.ts:895-935): a header chunk of the first segments up to
     ~chunk_size characters, one body chunk with the rest, and the caller's catch-up messages
     (SharedString's messagesSinceMSNChange: see catchup_messages) as JSON. The chunks are the legacy
     chunk object serialized by serializeAsMinSupportedVersion (snapshotChunks.ts:76-122), key order
-    included (`version` is undefined and JSON.stringify drops it)."""
-    specs = extract_segments_legacy(hdr, segs, interner)
+    included (`version` is undefined and JSON.stringify drops it). `specs`: the extracted segments when the caller
+    has them already (specs_from_summary of a legacy summary dump); `segs` is then unused."""
+    if specs is None:
+        specs = extract_segments_legacy(hdr, segs, interner)
     total = sum(n for _, n in specs)  # segmentsTotalLength (the extracted total wins a mismatch, 232-240)
     seq = hdr["minSeq"]
 
@@ -331,11 +358,26 @@ def emit_from_dump(dump: bytes, interner: ol.Interner, long_name, chunk_size: in
     return emit_v1(hdr, segs, interner, long_name, chunk_size)
 
 
+def emit_from_summary(summary: bytes, interner: ol.Interner, long_name, legacy: bool = False,
+                      catchup: Optional[List[dict]] = None, chunk_size: int = CHUNK_SIZE,
+                      catchup_blob: str = CATCHUP) -> dict:
+    """emit_v1 (or emit_legacy) over an engine / host-core summary dump (bytes) of the same mode."""
+    hdr, segs = ol.parse_dump(summary)
+    specs = specs_from_summary(hdr, segs, interner, long_name)
+    if legacy:
+        return emit_legacy(hdr, None, interner, catchup, chunk_size, catchup_blob, specs=specs)
+    return emit_v1(hdr, None, interner, long_name, chunk_size, specs=specs)
+
+
 def emit_batch(eng, docs, interner: ol.Interner, long_name, legacy: bool = False, catchup: Optional[List[dict]] = None,
-               chunk_size: int = CHUNK_SIZE, catchup_blob: str = CATCHUP) -> List[dict]:
+               chunk_size: int = CHUNK_SIZE, catchup_blob: str = CATCHUP, device: bool = False) -> List[dict]:
     """The summaries of many documents of an engine from one batched dump (Engine.dumps: one size launch and one
     fill launch for all of them): emit_from_dump per document of `docs` (None: every document), or
-    emit_legacy_from_dump with `legacy` (the same `catchup` for each)."""
+    emit_legacy_from_dump with `legacy` (the same `catchup` for each). `device`: the segments are extracted on the
+    device (Engine.summaries: the same two launches) and only serialized here; the same trees."""
+    if device:
+        return [emit_from_summary(x, interner, long_name, legacy, catchup, chunk_size, catchup_blob)
+                for x in eng.summaries(docs, legacy)]
     if legacy:
         return [emit_legacy_from_dump(d, interner, catchup, chunk_size, catchup_blob) for d in eng.dumps(docs)]
     return [emit_from_dump(d, interner, long_name, chunk_size) for d in eng.dumps(docs)]

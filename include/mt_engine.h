@@ -140,9 +140,12 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *   MT_VAR_DUMPS_PARALLEL (0 | 1): how mt_engine_dumps' fill kernel writes: 1 = every lane writes its own segment's
  *     record in 2- and 4-byte stores and the wave copies the texts together, 0 = one lane writes byte by byte (the
  *     single-document dump's writer); takes effect at the next mt_engine_dumps.
+ *   MT_VAR_SUMMARIES_PARALLEL (0 | 1): how mt_engine_summaries' fill kernel writes: 1 = the wave decides a pass of 64
+ *     rows at once, every run head and window row writes its own record and the wave copies the texts together,
+ *     0 = one lane walks the rows and writes (the host core's writer); takes effect at the next mt_engine_summaries.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
 enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4,
-       MT_VAR_DUMPS_PARALLEL = 5 };
+       MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -253,6 +256,16 @@ int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const 
  * fits cap: all or nothing, like mt_engine_get_texts; out == NULL is the size query. m == 0 returns 0 and
  * touches nothing. */
 int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap);
+/* The summary dump (mt_oplog.h) of every query's document: the segments SnapshotV1.extractSync (snapshotV1.ts:156-234,
+ * mode MT_SUMMARY_V1) or SnapshotLegacy.extractSync (snapshotlegacy.ts:179-242, mode MT_SUMMARY_LEGACY) yields,
+ * filtered, coalesced (canAppend of the grown run + matchProperties) and concatenated on the device, in the canonical
+ * dump's record layout: what a summary writer serializes, without the rows, overlap lists and local state it drops.
+ * The call contract is mt_engine_dumps': any order, repeats, docs == NULL for documents 0..m-1, promoted documents
+ * answer from their engines; returns the total byte count (<0: -MT_E_*; a document id out of range or an unknown
+ * mode: -MT_E_ARG) and always fills off_out[0..m]; `out` is written only when the total fits cap (all or nothing);
+ * out == NULL is the size query; m == 0 returns 0 and touches nothing. */
+int64_t mt_engine_summaries(mt_engine* e, int64_t m, const int64_t* docs, int32_t mode, int64_t* off_out, uint8_t* out,
+                            int64_t cap);
 /* MergeTree.getContainingSegment(pos, refSeq, clientId) (mergeTree.ts:1656-1667) per query; out[i].rid = -1
  * where there is no segment at pos[i]. */
 int32_t mt_engine_get_containing_segments(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,

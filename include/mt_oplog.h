@@ -225,6 +225,29 @@ enum {
                           MT_OPF_LOCAL records, so dumps of other logs are unchanged) */
 };
 
+/* ---- summary dump (binary; mt_engine_summaries) ---------------------------------------------
+ * The segments SnapshotV1.extractSync (snapshotV1.ts:156-234, MT_SUMMARY_V1) or SnapshotLegacy.extractSync
+ * (snapshotlegacy.ts:179-242, MT_SUMMARY_LEGACY) yields for a document, already filtered, coalesced and
+ * concatenated, in the canonical dump's layout (a reader of the dump reads it unchanged):
+ *
+ * header: the dump's six int32; nsegs = the number of emitted segments, nleaf = 0.
+ * record: one per emitted segment in document order; noverlap = ngroups = 0, localSeq = localRemovedSeq = leaf = 0;
+ *         properties (sorted by key id), derived values' contents and the MT_DF_HANDLE start as in the dump;
+ *         text: len units, the concatenated text (item ids) of the segment.
+ *   a coalesced settled run (v1: seq <= minSeq and not removed; legacy: every kept row): flags MT_DF_HAS_PROPS /
+ *     MT_DF_HANDLE only, seq 0, client -1, removedSeq = removedClient = 0; properties and start are those of the
+ *     run's first row, len is the run's length. A row joins the run in front of it while canAppend of the grown run
+ *     and matchProperties hold (textSegment.ts:63-68, sharedSequence.ts:57-60, permutationvector.ts:87-93,
+ *     properties.ts:61-92).
+ *   a window segment (v1 only: seq > minSeq, or removed above minSeq) is its row's record: seq, client,
+ *     MT_DF_REMOVED, removedSeq and removedClient are kept, the overlap list is dropped (as the v1 format drops it).
+ * v1 elides unacked rows (seq -1) and rows removed at or below minSeq (a pending local removal, -1, included); an
+ * elided row does not close a run. legacy keeps the rows of nonzero length sequenced at or below minSeq and not
+ * removed at or below it (a pending removal is kept), all as runs.
+ * seq 0 on settled records makes the format a fixed point: extracting from a summary dump gives the same segments
+ * as extracting from the canonical dump. */
+enum { MT_SUMMARY_V1 = 0, MT_SUMMARY_LEGACY = 1 };
+
 #define MT_FNV_OFFSET 0xcbf29ce484222325ULL
 #define MT_FNV_PRIME 0x100000001b3ULL
 
