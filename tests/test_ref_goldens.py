@@ -106,7 +106,11 @@ def kernel_variants(name):
     each fixture, whichever the engine would pick for the fixture's batch size. Config-2/3 profile: the LDS-image build
     (waves=1, mt_small_lds.hip), the 4-wave build (no spills) and the 8-wave build the config-3 bench runs; tiled profile (c4_large): the narrow LDS-heap kernel
     and the wide one; the other profiles have one build."""
-    _, w = load(name)
+    return variants_for(load(name)[1])
+
+
+def variants_for(w):
+    """kernel_variants for a workload (the fixtures of other families keep their own recipe)"""
     c = caps_for(w)
     if c["ncap"] <= 192 and w.mode != gen.MTG_MATRIX:
         return [dict(waves=1), dict(waves=4), dict(waves=8)]

@@ -303,8 +303,10 @@ FEATURE = {"lg_regen"} | set(rl.REF_NAMES)
 def _gpu_cases(build_id, profile, perm_only, with_promotion, feature=False):
     """the cases of a GPU batch: every fitting case, and cap_group_small (stated outcome: equal to the reference,
     after promotion where the build is too small). A document is promoted only by a fresh replay that holds its whole
-    history, in an engine without client features (include/mt_engine.h mt_engine_sync), so the documents THIS build
-    must promote are left out of its delta-stream and two-submit batches; the other builds keep them."""
+    history (include/mt_engine.h mt_engine_sync; client features do not prevent it, except in the tiled profile,
+    which then has no next one: mt_replay.hip next_ncap; tests/test_ref_reconnect.py GPU_CAP_OUTCOME pins that). The
+    documents THIS build must promote are left out of its delta-stream and two-submit batches; the other builds keep
+    them."""
     extra = [c for c in CAPS if c.name == "cap_group_small"] if not perm_only else []
     idx, cs = fitting(profile, perm_only, CASES + extra, refs=feature)
     mine = set().union(*[v for k, v in PROMOTED.items() if build_id.startswith(k)])

@@ -7,7 +7,10 @@ resubmitted messages carry one member per regenerated op. The reference (tools/r
 via tools/make_ref_goldens.py --regen) runs Client.regeneratePendingOp with each pending message and its
 segment group and records the ops it returns (MT_DELTA_REGEN events: findReconnectionPostition, length,
 op type) inside the delta stream, beside the callbacks. Compared: every document's digest (pending-group
-counts per segment included) and its whole delta stream.
+counts per segment included) and its whole delta stream. REGEN records replay only in the client-feature
+kernel (dcap > 0), of which each profile has one; the GPU test runs it under every `waves` / `wide` setting
+of the fixture's profile, which select no other kernel there (engine_settings). Hand-built reconnect cases
+(wide and out-of-order groups, reconnects before acks, the queue's limits): tests/test_ref_reconnect.py.
 """
 import glob
 import json
@@ -19,7 +22,7 @@ import pytest
 from fluidframework_amd import gen
 import core_host
 import regen_inject
-from test_ref_goldens import caps_for
+from test_ref_goldens import caps_for, variant_id, variants_for
 from make_goldens_sha import log_sha
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -53,12 +56,10 @@ def test_host_core_reconnect_matches_reference(name):
     assert not bad, f"regenerated ops / callbacks differ from the reference's on docs {bad[:8]}"
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", NAMES)
-def test_gpu_reconnect_matches_reference(name):
+def _gpu_reconnect(name, variant):
     from fluidframework_amd.engine import Engine
     z, w, rb, c = load(name)
-    eng = Engine(rb.ndocs, dcap=1 << 12, **c)
+    eng = Engine(rb.ndocs, dcap=1 << 12, **variant, **c)
     eng.start_collab(rb.local_long_id)
     eng.replay(rb)
     err, err_op = eng.errors()
@@ -68,3 +69,31 @@ def test_gpu_reconnect_matches_reference(name):
     n, h = eng.delta_state()
     bad = np.nonzero((n != z["nwords"]) | (h != z["hashes"]))[0]
     assert len(bad) == 0, f"HIP engine's regenerated ops / callbacks differ from the reference's on docs {bad[:8]}"
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_gpu_reconnect_matches_reference(name):
+    """the kernel build the engine picks for the batch"""
+    _gpu_reconnect(name, {})
+
+
+def engine_settings(name):
+    """the kernel-build settings of the fixture's own profile (test_ref_goldens.kernel_variants' rule over the
+    workload this fixture stores). REGEN records replay only in the client-feature build (dcap > 0), and each
+    profile has exactly one: replay_small (mt_prof_small.hip) and replay_huge (mt_prof_huge.hip) return it before
+    they look at `waves` or `wide`. The settings therefore select no other kernel here: each run repeats the
+    default one with another setting stored in the engine, and pins that the setting changes nothing."""
+    z = np.load(os.path.join(GOLDEN, f"refregen_{name}.npz"), allow_pickle=False)
+    return [v for v in variants_for(gen.Workload(**json.loads(str(z["workload"])))) if v]
+
+
+VARIANT_CASES = [(n, v) for n in NAMES for v in engine_settings(n)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,variant", VARIANT_CASES, ids=[variant_id(c) for c in VARIANT_CASES])
+def test_gpu_reconnect_matches_reference_under_every_setting(name, variant):
+    """the same client-feature kernel under every `waves` / `wide` setting of the profile (engine_settings)"""
+    _gpu_reconnect(name, variant)

@@ -462,6 +462,49 @@ def make_ranges(node: str) -> None:
           f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
 
 
+def make_reconnect(node: str) -> None:
+    """tests/golden/refreconnect.npz: the hand-built reconnect cases (tests/reconnect_logs.py: what one pending group
+    regenerates, findReconnectionPostition, reconnects before acks, the ring and the membership log at their limits, the
+    cap cases) replayed by the reference with Client.regeneratePendingOp: per document its digest, row count and whole
+    canonical dump (the oracle has no reconnect: nothing can stand in for a dump), the words of its delta stream with
+    their count and FNV-1a-64 (the MT_DELTA_REGEN events: position, length and type of every regenerated op) and the
+    SHA-256 of its SnapshotV1 summary at the end of the log. Every case's witness must hold on the reference's dump and
+    its stated op counts must be the reference's."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reconnect_logs as rc
+    cs = rc.cases() + rc.caps()
+    b = rc.batch(cs)
+    it = cs[0].log.interner
+    cuts = [int(n) for n in np.diff(b.op_off)]  # summarized at the end of the log
+    d = os.path.join(SCRATCH, "reconnect")
+    dumps, info, secs, (trees, loaded, tail_err, tail_msgs, load_err, load_msgs) = run_reference(
+        b, d, node, cuts, interner=it, extra=("--deltas",))
+    parsed = [ol.parse_dump(x) for x in dumps]
+    words = np.fromfile(os.path.join(d, "ref_deltas.bin"), "<i4")
+    woff = np.fromfile(os.path.join(d, "ref_delta_off.bin"), "<i8")
+    per = [words[woff[i]: woff[i + 1]] for i in range(b.ndocs)]
+    for c, p, w in zip(cs, parsed, per):
+        if not c.witness(*p):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+        got = tuple(len(e) for e in rc.regen_events(w))
+        if got != c.nops:
+            raise RuntimeError(f"{c.name}: the reference regenerates {got} ops, the case states {c.nops}")
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refreconnect.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=np.asarray([fnv1a64(x) for x in dumps], np.uint64),
+        nrows=np.asarray([p[0]["nsegs"] for p in parsed], np.int64), dumps=np.frombuffer(b"".join(dumps), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(x) for x in dumps])]).astype(np.int64),
+        delta_nwords=np.diff(woff).astype(np.int64), delta_hashes=np.asarray([words_fnv(x) for x in per], np.uint64),
+        delta_words=np.concatenate(per).astype(np.int32), delta_off=woff.astype(np.int64),
+        snap_sha256=np.asarray([hashlib.sha256(canonical_tree(t).encode()).hexdigest() for t in trees]),
+        source=("packages/dds/merge-tree/src + sequence sharedSequence.ts SubSequence + matrix permutationvector.ts "
+                "(reference, type-erased by tools/ts_erase.py) under node by tools/ref_replay.mjs --deltas with "
+                "snapshots.json: Client.regeneratePendingOp on reconnect; logs: tests/reconnect_logs.py"))
+    print(f"refreconnect: {b.ndocs} docs, {b.nops} records, {sum(len(c.nops) for c in cs)} regenerated groups, "
+          f"{sum(sum(c.nops) for c in cs)} regenerated ops, every witness and stated count holds; "
+          f"{len(load_msgs)} summaries do not load", flush=True)
+
+
 def make_inserts(node: str) -> None:
     """tests/golden/refinserts.npz: the hand-built insert cases (tests/insert_logs.py: tie walks over tombstones and
     pending rows, search alignment on 256-slot boundaries, row splits by offset, child index and child count, node
@@ -1235,6 +1278,7 @@ def main() -> None:
     ap.add_argument("--subseq", action="store_true", help="write the SubSequence fixtures (refsubseq_*.npz) only")
     ap.add_argument("--zamboni", action="store_true", help="write the zamboni edge-case fixture (refzamboni.npz) only")
     ap.add_argument("--ranges", action="store_true", help="write the wide range-edit fixture (refranges.npz) only")
+    ap.add_argument("--reconnect", action="store_true", help="write the hand-built reconnect fixture (refreconnect.npz) only")
     ap.add_argument("--inserts", action="store_true", help="write the insert placement / split fixture (refinserts.npz) only")
     ap.add_argument("--props", action="store_true", help="write the property-manager fixture (refprops.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
@@ -1248,6 +1292,9 @@ def main() -> None:
         return
     if args.ranges:
         make_ranges(args.node)
+        return
+    if args.reconnect:
+        make_reconnect(args.node)
         return
     if args.inserts:
         make_inserts(args.node)
