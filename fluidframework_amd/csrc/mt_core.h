@@ -468,6 +468,13 @@ enum { PH_APPLY, PH_ZAMBONI, PH_FIND, PH_MAP, PH_SPLIT, PH_ACK, PH_TEXT, PH_HEAP
        PH_VISIT, PH_PLACE, /* a range op's visit; an insert's row set-up after placement */
        PH_C_INS, PH_C_RANGE, PH_C_WROWS, PH_C_WMISS, PH_C_SCOUR, PH_C_PACK, /* event counts, not cycles */
        PH_C_HEAPN, PH_C_POP, PH_C_PUSH,
+       /* inside a flat range op (range_op): its scan, the end rows' id reads, the two splits, the look-ups of a row
+        * by its id (one row, both rows), the lane-parallel visit; range ops by the rows they split (none, one, two)
+        * and the second splits whose row the first split may have moved. RRID, RSLOT1 and RSLOT2 clocked the id reads
+        * and look-ups range_op made before it carried the slots: they read 0 now and keep the
+        * columns of the two profiles aligned */
+       PH_RSCAN, PH_RRID, PH_RSPLIT1, PH_RSPLIT2, PH_RSLOT1, PH_RSLOT2, PH_RVISIT,
+       PH_C_RSPLIT0, PH_C_RSPLIT1, PH_C_RSPLIT2, PH_C_RMOVED,
        PH_N };
 #if defined(MT_PROF) && defined(__HIP_DEVICE_COMPILE__)
 struct ProfScope { /* no live register across the scope: the LDS counter takes -start at entry and +end at exit */
@@ -2967,7 +2974,8 @@ struct Replica {
     /* Make room at child index j of leaf n; returns slot for the new row (after any split). */
     /* dup: the new slot starts as a copy of the row before it (j >= 1; a split's right part), made
      * by the same parallel shift instead of a separate row copy */
-    MT_HD int32_t leaf_insert_slot(int32_t n, int32_t j, bool dup = false) {
+    /* nnOut: the new leaf, if making room split leaf n */
+    MT_HD int32_t leaf_insert_slot(int32_t n, int32_t j, bool dup = false, int32_t* nnOut = nullptr) {
         MT_PROF_SCOPE(PH_LEAFINS);
         int32_t c = nch[n];
         slab_shift_right(n, dup ? j - 1 : j, c);
@@ -2978,9 +2986,19 @@ struct Replica {
         if (c + 1 >= MAXN) {
             int32_t nn = split_node(n);
             if (nn < 0) return -1;
+            if (nnOut) *nnOut = nn;
             if (j >= 4) return nn * MAXN + (j - 4);
         }
         return n * MAXN + j;
+    }
+    /* Where the row of slot x sits once `shift` slots were opened at child index ji of leaf n and the leaf, if that
+     * filled it, split 4 + 4 into n and nn (split_node moves children 4..7; nn < 0: no leaf split). Rows of other
+     * leaves keep their slots: a slot names its leaf's node, not the leaf's place in document order. */
+    MT_HD static int32_t slot_after_insert(int32_t x, int32_t n, int32_t ji, int32_t shift, int32_t nn) {
+        if (x < 0 || x / MAXN != n) return x;
+        int32_t jx = x & (MAXN - 1);
+        if (jx >= ji) jx += shift;
+        return nn >= 0 && jx >= 4 ? nn * MAXN + (jx - 4) : n * MAXN + jx;
     }
 
     /* ---- text arena -------------------------------------------------------------------- */
@@ -3046,7 +3064,8 @@ struct Replica {
      * write pass also leaves an empty slot between the halves for the new row (rows after the split move two
      * slots), which *gapOut returns — the shift leaf_insert_slot would make with a second read of the leaf */
     MT_HD int32_t split_row_par(int32_t n, int32_t j, int32_t off, int32_t* rsOut, int32_t* gapOut = nullptr,
-                                const HotRow* pre = nullptr, int32_t preC = -1, int32_t* ridOut = nullptr) {
+                                const HotRow* pre = nullptr, int32_t preC = -1, int32_t* ridOut = nullptr,
+                                int32_t* track = nullptr) {
         constexpr int CW = (int)(sizeof(typename HT::Cold) / 4);
         static_assert(W::N >= CW && W::N >= MAXN, "a lane per cold dword and per slot");
         const int32_t l = w.lane();
@@ -3086,12 +3105,14 @@ struct Replica {
                 z.len(rs) = off < len0 ? len0 - off : 0;
             }
         }
+        int32_t nn = -1;
         if (willSplit) {
             MT_PROF_SCOPE(PH_LEAFINS);
-            int32_t nn = split_node(n);
+            nn = split_node(n);
             if (nn < 0) return -1;
             if (j + 1 >= 4) rs = nn * MAXN + (j + 1 - 4);
         }
+        if (track) *track = slot_after_insert(*track, n, j + 1, 1 + g, nn);
         /* the left part stays at n*8+j unless the leaf split moved children 4..7 (then it sits just before the
          * new slot, in the new leaf) */
         int32_t ls = willSplit && j >= 4 ? rs - 1 : s0;
@@ -3151,16 +3172,25 @@ struct Replica {
     /* ridOut: the right part's row id (the caller need not read back what the split wrote) */
     MT_HD int32_t split_row(int32_t t, int32_t off, int32_t* rsOut = nullptr, int32_t* gapOut = nullptr,
                             const HotRow* pre = nullptr, int32_t preC = -1, int32_t* ridOut = nullptr) {
+        return split_slot(leaf_at(t >> 3) * MAXN + (t & 7), off, rsOut, gapOut, pre, preC, ridOut);
+    }
+    /* split_row of the row at slot s0 (no leaf-order look-up). track: in, the slot of a row the caller follows; out,
+     * that row's slot after the split (the split row itself: its left part, which keeps the id), from what the split
+     * holds already: the slab shift moves the rows after the split one slot, a leaf split moves children 4..7 */
+    MT_HD int32_t split_slot(int32_t s0, int32_t off, int32_t* rsOut = nullptr, int32_t* gapOut = nullptr,
+                             const HotRow* pre = nullptr, int32_t preC = -1, int32_t* ridOut = nullptr,
+                             int32_t* track = nullptr) {
         MT_PROF_SCOPE(PH_SPLIT);
-        int32_t n = leaf_at(t >> 3), j = t & 7;
-        int32_t s0 = n * MAXN + j;
+        int32_t n = s0 / MAXN, j = s0 & (MAXN - 1);
         if constexpr (W::N >= 64) {
-            if (!dl_on() && !refs_on()) return split_row_par(n, j, off, rsOut, gapOut, pre, preC, ridOut);
+            if (!dl_on() && !refs_on()) return split_row_par(n, j, off, rsOut, gapOut, pre, preC, ridOut, track);
         }
         if (z.flags(s0) & RF_MARKER) return s0; /* Marker.createSplitSegmentAt -> undefined */
         bool willSplit = nch[n] + 1 >= MAXN;
-        int32_t rs = leaf_insert_slot(n, j + 1, true); /* rs starts as a copy of the row */
+        int32_t nn = -1;
+        int32_t rs = leaf_insert_slot(n, j + 1, true, &nn); /* rs starts as a copy of the row */
         if (rs < 0) return -1;
+        if (track) *track = slot_after_insert(*track, n, j + 1, 1, nn);
         /* the left part stays at n*8+j unless the leaf split moved children 4..7 (then it sits just
          * before the new slot, in the new leaf) */
         int32_t ls = n * MAXN + j;
@@ -4950,6 +4980,7 @@ struct Replica {
         int32_t tf = -1, Pf = 0, vf = 0, tg = -1, Pg = 0, vg = 0, sf = -1, sg = -1;
         {
             MT_PROF_SCOPE(PH_FIND);
+            MT_PROF_SCOPE(PH_RSCAN);
             const bool loc = is_local(client);
             constexpr int NB = W::N >= 64 ? MT_SCAN_NB : 1; /* wave blocks whose loads are issued together */
             bool done = false;
@@ -5010,31 +5041,33 @@ struct Replica {
         }
         if (tf < 0) return;
         int32_t sa = sf, sb = sg; /* no split: the rows stay where the scan found them */
+        MT_PROF_COUNT(Pf < start ? (Pg + vg > end ? PH_C_RSPLIT2 : PH_C_RSPLIT1) : Pg + vg > end ? PH_C_RSPLIT1 : PH_C_RSPLIT0, 1);
         if (Pf < start || Pg + vg > end) {
-            int32_t ridLast = z.RID(sg);
-            int32_t ridFirst = z.RID(sf);
-            int32_t sl = sg; /* the last row's slot, while nothing has moved it */
+            /* The end rows' slots are carried through the splits: a slot names its leaf's node, so a split moves only
+             * rows of the leaf it splits in, by the slab shift and, if the leaf fills, the 4 + 4 leaf split, both known
+             * to the split (split_slot's track). No row is looked up by its id again. */
             if (Pf < start) { /* start falls inside the first row: split it; its right part is first */
-                int32_t rs = -1, rr = -1;
-                if (split_row(tf, start - Pf, &rs, nullptr, nullptr, -1, &rr) < 0 || rs < 0) return;
-                sl = -1;
-                if (tf == tg) {
-                    ridLast = rr;
-                    sl = rs;
+                MT_PROF_SCOPE(PH_RSPLIT1);
+                int32_t rs = -1;
+                if (split_slot(sf, start - Pf, &rs, nullptr, nullptr, -1, nullptr, &sb) < 0 || rs < 0) return;
+                sa = rs;
+                if (tf == tg) { /* one row: its right part is the last row too */
+                    sb = rs;
                     vg = Pf + vf - start;
                     Pg = start;
                 }
-                ridFirst = rr;
             }
             if (Pg + vg > end) { /* end falls inside the last row: split it; its left part keeps the id */
-                if (sl < 0) sl = slot_of(ridLast, -1);
-                if (sl < 0) {
+                MT_PROF_SCOPE(PH_RSPLIT2);
+                MT_PROF_COUNT(PH_C_RMOVED, Pf < start && tf != tg ? 1 : 0);
+                if (sb < 0) {
                     fail(E_ASSERT);
                     return;
                 }
-                if (split_row(kpos(sl / MAXN) * MAXN + (sl & (MAXN - 1)), end - Pg) < 0) return;
+                /* (where the first row is the row being split, it is the left part: track follows the id) */
+                sb = split_slot(sb, end - Pg, nullptr, nullptr, nullptr, -1, nullptr, &sa);
+                if (sb < 0) return;
             }
-            slot_of2(ridFirst, ridLast, &sa, &sb);
             if (sa < 0 || sb < 0) {
                 fail(E_ASSERT);
                 return;
@@ -5049,6 +5082,7 @@ struct Replica {
             visit_run(sa, sb, refSeq, client, leaf, true);
             return;
         }
+        MT_PROF_SCOPE(PH_RVISIT);
         int32_t ta = kpos(sa / MAXN) * MAXN + (sa & (MAXN - 1));
         int32_t tb = kpos(sb / MAXN) * MAXN + (sb & (MAXN - 1));
         for (int32_t b = ta & ~3; b <= tb; b += 4 * W::N) {

@@ -12,7 +12,9 @@ from fluidframework_amd import native
 PHASES = ["APPLY", "ZAMBONI", "FIND", "MAP", "SPLIT", "ACK", "TEXT", "HEAP", "SCOUR", "PACK", "APPEND", "CAND", "S1load", "S2walk", "S3compact", "P1leaf", "P2interior", "INSROW", "LEAFINS",
           "WIN", "TFIND", "LFIND", "ROPE", "RESTAT", "VISIT", "PLACE",
           "#ins", "#range", "#winrows", "#winmiss", "#scour", "#pack",
-          "#heapsize", "#pop", "#push"]
+          "#heapsize", "#pop", "#push",
+          "Rscan", "Rrid", "Rsplit1", "Rsplit2", "Rslot1", "Rslot2", "Rvisit",  # inside a flat range op
+          "#rsplit0", "#rsplit1", "#rsplit2", "#rmoved"]
 LIB = os.environ.get("MT_PROF_LIB") or native.lib_path("libmtreplay_prof.so")  # MT_PROF_LIB: a prebuilt copy
 
 
