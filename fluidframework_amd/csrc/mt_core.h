@@ -5480,6 +5480,248 @@ struct Replica {
         return true;
     }
 
+    /* ---- marker queries: MergeTree.findTile / getStackContext in the local view ------------------------------
+     * (mergeTree.ts:1796-1822 and 1783-1793; Client.findTile client.ts:1075, Client.getStackContext client.ts:948:
+     * always the replica's own client under UniversalSequenceNumber, so there is no perspective to refuse.)
+     * A label is a string inside an array-valued property; the host interns the array as one value id, so a query
+     * names the key id of referenceTileLabels / referenceRangeLabels and `set`, a bitmap over the 2^15 host value
+     * ids (TQ_SET_WORDS words) whose bit v says "value v is an array that holds the label". Derived values are never
+     * arrays; the falsy bit is masked off first, as marker_by_id does. A label key an annotate changed on a marker
+     * (mkMask) is refused: the reference's block caches (rightmostTiles, rangeStacks) are rebuilt by blockUpdate
+     * only, which annotateRange does not call, so its answer then depends on block-update history.
+     * A result is TQ_WORDS words: row id, generation, index in walkAllSegments order, local position, refType. */
+    enum { TQ_NONE = 0, TQ_FOUND = 1, TQ_REFUSED = 2 };
+    enum { TQ_WORDS = 5, TQ_SET_WORDS = 1024 };
+    enum { REFT_TILE = 1, REFT_BEGIN = 2, REFT_END = 4 }; /* ops.ts:6-15 */
+    MT_HD static bool label_in(const uint32_t* set, int32_t v) {
+        v &= ~MT_VALUE_FALSY;
+        return v != 0 && v < MT_VALUE_DERIVED && ((set[v >> 5] >> (v & 31)) & 1u) != 0;
+    }
+    /* Marker.hasTileLabel / hasRangeLabel (mergeTree.ts:620-646): a marker whose refType has one of `bits`, with
+     * properties, whose label key (slot) holds a value of the set */
+    MT_HD bool labelled(int32_t s, int32_t slot, const uint32_t* set, int32_t bits) {
+        const uint8_t fl = z.flags(s);
+        if (!(fl & RF_MARKER) || !(fl & RF_PROPS)) return false;
+        return ((int32_t)cold(s).toff & bits) != 0 && label_in(set, cold(s).pv[slot]);
+    }
+    /* the slot of a key the document has seen, -1 if none (key_slot would add it) */
+    MT_HD int32_t label_slot(int32_t key) const {
+        for (int32_t k = 0; k < zh->nkeys; k++)
+            if (keys[k] == key) return k;
+        return -1;
+    }
+    MT_HD void tile_words(int32_t s, int32_t ordinal, int32_t pos, int32_t* o) {
+        const int32_t rid = (int32_t)z.RID(s);
+        o[0] = rid;
+        o[1] = z.RGEN(rid);
+        o[2] = ordinal;
+        o[3] = pos;
+        o[4] = (int32_t)cold(s).toff;
+    }
+    /* findTile. search / backwardSearch with recordTileStart / tileShift (1030-1069): blocks contribute their
+     * rightmost / leftmost tiles, which addNodeReferences (262-300) takes from markers of positive local net length;
+     * the segment the search stops at counts whatever its length. Both directions are one walk in document order,
+     * since the local start P of a row never decreases:
+     *   preceding: the last labelled tile before the stop row, the first row with P <= pos < P + len (none when pos
+     *     is undefined (< 0) or at or past the length: the whole document);
+     *   else: none when pos > length; the stop row is the last with P <= pos (a zero-length last row included), the
+     *     answer the first labelled tile after it.
+     * A labelled stop row is the answer either way. Returns TQ_*; out: TQ_WORDS words (out[0] = -1 unless found). */
+    MT_HD int32_t find_tile(int32_t pos, bool preceding, int32_t key, const uint32_t* set, int32_t* out) {
+        out[0] = -1;
+        for (int i = 1; i < TQ_WORDS; i++) out[i] = 0;
+        const int32_t slot = label_slot(key);
+        if (slot < 0) return TQ_NONE;
+        if (zh->mkMask & (1 << slot)) return TQ_REFUSED;
+        if (!preceding && pos > length_local()) return TQ_NONE;
+        int32_t P = 0, ord = 0, best = -1, bo = 0, bp = 0, stop = -1, so = 0, sp = 0;
+        bool done = false;
+        for (int32_t k = 0; kvalid(k) && !done; k = knext(k)) {
+            const int32_t lf = leaf_at(k), c = nch[lf];
+            for (int32_t j = 0; j < c && !done; j++, ord++) {
+                const int32_t s = lf * MAXN + j, v = local_len(s);
+                if (preceding ? (pos >= 0 && v > 0 && pos < P + v) : (pos >= 0 && P <= pos)) {
+                    stop = s, so = ord, sp = P;
+                    done = preceding;
+                } else if (v > 0 && labelled(s, slot, set, REFT_TILE)) {
+                    best = s, bo = ord, bp = P;
+                    done = !preceding;
+                }
+                P += v;
+            }
+        }
+        if (stop >= 0 && labelled(stop, slot, set, REFT_TILE)) best = stop, bo = so, bp = sp;
+        if (best < 0) return TQ_NONE;
+        tile_words(best, bo, bp, out);
+        return TQ_FOUND;
+    }
+    /* the next pass of dump_wave's walk: 8 leaves x 8 rows from leaf position k on; the lane's row, or -1 */
+    MT_HD int32_t pass_row(int32_t& k, bool& more) {
+        const int32_t li = w.lane() >> 3, j = w.lane() & (MAXN - 1);
+        int32_t leaf = -1;
+        for (int32_t i = 0; i < MAXN && more; i++) {
+            const int32_t lf = leaf_at(k);
+            if (i == li) leaf = lf;
+            k = knext(k);
+            more = kvalid(k);
+        }
+        return leaf >= 0 && j < nch[leaf] ? leaf * MAXN + j : -1;
+    }
+    /* find_tile by the whole wave: every lane classifies its own row of the pass (local length, an exclusive scan
+     * for its local start, the label test), one ballot per question. preceding: the highest hit below the stop lane,
+     * carried over the passes until a pass holds the stop row; else the stop row is carried (the highest lane with
+     * P <= pos so far) and the first hit behind it ends the walk. Every lane must call this and gets the result;
+     * the one-lane host build takes the serial form. */
+    MT_HD int32_t find_tile_wave(int32_t pos, bool preceding, int32_t key, const uint32_t* set, int32_t* out) {
+        if constexpr (W::N < MAXN * MAXN) {
+            return find_tile(pos, preceding, key, set, out);
+        } else {
+            out[0] = -1;
+            for (int i = 1; i < TQ_WORDS; i++) out[i] = 0;
+            const int32_t slot = label_slot(key);
+            if (slot < 0) return TQ_NONE;
+            if (zh->mkMask & (1 << slot)) return TQ_REFUSED;
+            if (!preceding && pos > length_local()) return TQ_NONE;
+            const uint64_t below = (1ull << w.lane()) - 1;
+            int32_t P0 = 0, ord0 = 0, best = -1, bo = 0, bp = 0, stop = -1, so = 0, sp = 0;
+            int32_t k = 0;
+            bool more = kvalid(0), done = false;
+            while (more && !done) {
+                const int32_t s = pass_row(k, more);
+                const int32_t v = s >= 0 ? local_len(s) : 0;
+                int32_t tot;
+                const int32_t P = P0 + w.excl_scan(v, &tot);
+                const uint64_t valid = w.ballot(s >= 0);
+                const int32_t ord = ord0 + __builtin_popcountll(valid & below);
+                uint64_t hm = w.ballot(s >= 0 && v > 0 && labelled(s, slot, set, REFT_TILE));
+                if (preceding) {
+                    const uint64_t sm = w.ballot(pos >= 0 && v > 0 && pos >= P && pos < P + v);
+                    if (sm) {
+                        const int sl = W::ffs(sm);
+                        hm &= (1ull << sl) - 1;
+                        stop = w.bcast(s, sl), so = w.bcast(ord, sl), sp = w.bcast(P, sl);
+                        done = true;
+                    }
+                    if (hm) {
+                        const int b = 63 - __builtin_clzll(hm);
+                        best = w.bcast(s, b), bo = w.bcast(ord, b), bp = w.bcast(P, b);
+                    }
+                } else {
+                    const uint64_t pm = w.ballot(s >= 0 && pos >= 0 && P <= pos);
+                    if (pm) {
+                        const int sl = 63 - __builtin_clzll(pm);
+                        stop = w.bcast(s, sl), so = w.bcast(ord, sl), sp = w.bcast(P, sl);
+                    }
+                    hm &= ~pm;
+                    if (hm) {
+                        const int b = W::ffs(hm);
+                        best = w.bcast(s, b), bo = w.bcast(ord, b), bp = w.bcast(P, b);
+                        done = true;
+                    }
+                }
+                P0 += tot;
+                ord0 += __builtin_popcountll(valid);
+            }
+            if (stop >= 0 && labelled(stop, slot, set, REFT_TILE)) best = stop, bo = so, bp = sp;
+            if (best < 0) return TQ_NONE;
+            tile_words(best, bo, bp, out);
+            return TQ_FOUND;
+        }
+    }
+    /* getStackContext for one label. The reference's search shifts over whole blocks with applyStackDelta (228-243),
+     * which applies a block's reduced stack item by item. Every stack has the form E*B* (an end is pushed only on an
+     * empty stack or on an end, a begin only pops from the top), so applying a block's reduced stack item by item
+     * equals applying its markers one by one with applyRangeReference (245-260): the flat walk below is the
+     * reference's answer. Applied: every labelled NestBegin | NestEnd marker of positive local net length before the
+     * stop row (rangeShift, 1008-1028), then the stop row itself if it is one (recordRangeLeaf, 997-1007); the
+     * NestBegin test comes first for a marker with both bits. The E*B* form also means two counters describe the
+     * stack, so sizing needs no buffer. out (cap entries of TQ_WORDS words, bottom first; NULL: sizes only) is never
+     * written at or past cap; *depth = the final depth, *high = the deepest the walk got. Only lane 0 writes. */
+    struct StackWalk {
+        int32_t nE, nB, high;
+    };
+    MT_HD void stack_apply(StackWalk& k, bool begin, bool writer, int32_t s, int32_t ord, int32_t P, int32_t* out,
+                           int32_t cap) {
+        if (!begin && k.nB > 0) { /* the top is a begin: pop */
+            k.nB--;
+            return;
+        }
+        const int32_t d = k.nE + k.nB;
+        if (writer && out && d < cap) tile_words(s, ord, P, out + (int64_t)d * TQ_WORDS);
+        if (begin)
+            k.nB++;
+        else
+            k.nE++;
+        if (d + 1 > k.high) k.high = d + 1;
+    }
+    MT_HD int32_t stack_context(int32_t pos, int32_t key, const uint32_t* set, int32_t* out, int32_t cap,
+                                int32_t* depth, int32_t* high) {
+        *depth = *high = 0;
+        const int32_t slot = label_slot(key);
+        if (slot < 0) return TQ_NONE;
+        if (zh->mkMask & (1 << slot)) return TQ_REFUSED;
+        StackWalk sk = {0, 0, 0};
+        int32_t P = 0, ord = 0;
+        bool done = false;
+        for (int32_t k = 0; kvalid(k) && !done; k = knext(k)) {
+            const int32_t lf = leaf_at(k), c = nch[lf];
+            for (int32_t j = 0; j < c && !done; j++, ord++) {
+                const int32_t s = lf * MAXN + j, v = local_len(s);
+                done = pos >= 0 && v > 0 && pos < P + v;
+                if (v > 0 && labelled(s, slot, set, REFT_BEGIN | REFT_END))
+                    stack_apply(sk, ((int32_t)cold(s).toff & REFT_BEGIN) != 0, w.lane() == 0, s, ord, P, out, cap);
+                P += v;
+            }
+        }
+        *depth = sk.nE + sk.nB;
+        *high = sk.high;
+        return TQ_FOUND;
+    }
+    /* stack_context by the whole wave: the lanes classify their rows of the pass in parallel (as find_tile_wave);
+     * the few hit lanes are then applied in bit order by a wave-uniform loop over the ballot, the hit lane writing
+     * its own entry. Markers are sparse, so the push / pop stays scalar. Every lane must call this. */
+    MT_HD int32_t stack_context_wave(int32_t pos, int32_t key, const uint32_t* set, int32_t* out, int32_t cap,
+                                     int32_t* depth, int32_t* high) {
+        if constexpr (W::N < MAXN * MAXN) {
+            return stack_context(pos, key, set, out, cap, depth, high);
+        } else {
+            *depth = *high = 0;
+            const int32_t slot = label_slot(key);
+            if (slot < 0) return TQ_NONE;
+            if (zh->mkMask & (1 << slot)) return TQ_REFUSED;
+            const uint64_t below = (1ull << w.lane()) - 1;
+            StackWalk sk = {0, 0, 0};
+            int32_t P0 = 0, ord0 = 0, k = 0;
+            bool more = kvalid(0), done = false;
+            while (more && !done) {
+                const int32_t s = pass_row(k, more);
+                const int32_t v = s >= 0 ? local_len(s) : 0;
+                int32_t tot;
+                const int32_t P = P0 + w.excl_scan(v, &tot);
+                const uint64_t valid = w.ballot(s >= 0);
+                const int32_t ord = ord0 + __builtin_popcountll(valid & below);
+                const bool hit = s >= 0 && v > 0 && labelled(s, slot, set, REFT_BEGIN | REFT_END);
+                const int32_t begin = hit && ((int32_t)cold(s).toff & REFT_BEGIN) ? 1 : 0;
+                uint64_t hm = w.ballot(hit);
+                const uint64_t sm = w.ballot(pos >= 0 && v > 0 && pos >= P && pos < P + v);
+                if (sm) { /* the stop row and what lies before it */
+                    hm &= (2ull << W::ffs(sm)) - 1;
+                    done = true;
+                }
+                for (; hm; hm &= hm - 1) {
+                    const int b = W::ffs(hm);
+                    stack_apply(sk, w.bcast(begin, b) != 0, w.lane() == b, s, ord, P, out, cap);
+                }
+                P0 += tot;
+                ord0 += __builtin_popcountll(valid);
+            }
+            w.sync();
+            *depth = sk.nE + sk.nB;
+            *high = sk.high;
+            return TQ_FOUND;
+        }
+    }
+
     /* ---- reconnect: Client.regeneratePendingOp (client.ts:706-762, 855-893) -------------- */
     /* findReconnectionPostition (client.ts:675-705): the lengths of the rows before slot s that are
      * inserted (no pending localSeq, or one <= lseq) and not removed (or removed by a local op after lseq) */

@@ -257,6 +257,20 @@ void mth_stats(mth_store* s, int64_t doc, int32_t* out8) {
     });
 }
 
+/* MergeTree.findTile in the local view (Replica::find_tile; pos < 0: undefined): 0 none, 1 found, 2 refused (the
+ * label key was annotated on a marker; the engine's MT_E_UNSUPPORTED); out5 = {rid, gen, ordinal, position, refType}.
+ * set: the 1,024-word bitmap of the value ids that are arrays holding the label. */
+int32_t mth_find_tile(mth_store* s, int64_t doc, int32_t pos, int32_t preceding, int32_t key, const uint32_t* set,
+                      int32_t* out5) {
+    return with_replica(s, doc, [&](auto& r) { return r.find_tile(pos, preceding != 0, key, set, out5); });
+}
+/* MergeTree.getStackContext for one label in the local view (Replica::stack_context): the status as above (1: answered);
+ * out: at most cap entries of 5 words, bottom first (NULL: sizes only); dh2 = {final depth, deepest depth of the walk} */
+int32_t mth_stack_context(mth_store* s, int64_t doc, int32_t pos, int32_t key, const uint32_t* set, int32_t* out,
+                          int32_t cap, int32_t* dh2) {
+    return with_replica(s, doc, [&](auto& r) { return r.stack_context(pos, key, set, out, cap, &dh2[0], &dh2[1]); });
+}
+
 } /* extern "C" */
 
 /* MergeTree.posFromRelativePos in the local view (long_client < 0) or (ref_seq, long_client); returns 0 and

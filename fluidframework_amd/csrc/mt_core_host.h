@@ -37,6 +37,10 @@ int64_t mth_summary(mth_store* s, int64_t doc, int32_t mode, uint8_t* out, int64
 uint64_t mth_digest(mth_store* s, int64_t doc);
 void mth_stats(mth_store* s, int64_t doc, int32_t* out8);
 int32_t mth_containing(mth_store* s, int64_t doc, int32_t pos, int32_t ref_seq, int32_t long_client, int32_t* out6);
+int32_t mth_find_tile(mth_store* s, int64_t doc, int32_t pos, int32_t preceding, int32_t key, const uint32_t* set,
+                      int32_t* out5);
+int32_t mth_stack_context(mth_store* s, int64_t doc, int32_t pos, int32_t key, const uint32_t* set, int32_t* out,
+                          int32_t cap, int32_t* dh2);
 #ifdef __cplusplus
 }
 #endif

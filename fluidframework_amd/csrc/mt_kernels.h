@@ -877,6 +877,64 @@ __global__ __launch_bounds__(WG) void k_summaries(Store<HT> st, int64_t m, const
         (void)r.summary(out + o, cap, mode);
 }
 
+/* ---- batched marker queries (mt_engine_find_tiles / mt_engine_stack_contexts): the local view only, so no
+ * perspective; q.a = the position (< 0: undefined), q.b = preceding (find_tiles). `key` is the label key's id and
+ * `set` the call's one label as a bitmap over the host's value ids (Replica::label_in). The walks keep no scratch in
+ * the document block. A refused query (the label key was annotated on a marker) has status MT_E_UNSUPPORTED. ---- */
+#ifndef MT_TILES_PARALLEL_DEFAULT
+#define MT_TILES_PARALLEL_DEFAULT true /* k_find_tiles / k_stacks: the wave forms or the serial ones */
+#endif
+static_assert(sizeof(mt_tile_ref) == 4 * MT_TILE_WORDS, "mt_tile_ref is Replica::tile_words' five words");
+/* MergeTree.findTile per query: out[slot] (rid -1: none or refused), status[slot] */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_find_tiles(Store<HT> st, int64_t m, const ReadQ* qs, int32_t key,
+                                                  const uint32_t* set, int32_t* out, int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int32_t res[MT_TILE_WORDS];
+    int32_t rc;
+    if constexpr (PAR)
+        rc = r.find_tile_wave(q.a, q.b != 0, key, set, res);
+    else
+        rc = r.find_tile(q.a, q.b != 0, key, set, res);
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < MT_TILE_WORDS; i++) out[(int64_t)q.slot * MT_TILE_WORDS + i] = res[i];
+        status[q.slot] = rc == 2 ? MT_E_UNSUPPORTED : MT_OK;
+    }
+}
+/* MergeTree.getStackContext per query, sized: count[slot] = the final depth, high[slot] = the deepest the walk gets
+ * (the window k_stacks needs); both 0 for a refused query */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_stack_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int32_t key,
+                                                   const uint32_t* set, int32_t* count, int64_t* high,
+                                                   int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int32_t d = 0, hw = 0;
+    const int32_t rc = r.stack_context_wave(q.a, key, set, nullptr, 0, &d, &hw);
+    if (threadIdx.x == 0) count[q.slot] = d, high[q.slot] = hw, status[q.slot] = rc == 2 ? MT_E_UNSUPPORTED : MT_OK;
+}
+/* query i's stack in its window out[off[slot], off[slot + 1]) (entries of MT_TILE_WORDS words; the host's prefix sum
+ * of k_stack_sizes' high-water marks) and nowhere else: the first count[slot] entries are the answer, bottom first.
+ * PAR: the wave form; else the serial walk, lane 0 writing: the same entries either way. */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_stacks(Store<HT> st, int64_t m, const ReadQ* qs, int32_t key,
+                                              const uint32_t* set, const int64_t* off, int32_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    int32_t d, hw;
+    const int32_t c = cap > 0x7fffffff ? 0x7fffffff : (int32_t)cap;
+    if constexpr (PAR)
+        (void)r.stack_context_wave(q.a, key, set, out + o * MT_TILE_WORDS, c, &d, &hw);
+    else
+        (void)r.stack_context(q.a, key, set, out + o * MT_TILE_WORDS, c, &d, &hw);
+}
+
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
  * out[2i+1] = its generation; *n = the segment count (writes at most cap pairs) */
 template <class HT>
@@ -1026,6 +1084,7 @@ struct mt_engine {
     bool texts_packed = MT_TEXTS_PACKED_DEFAULT; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
     bool dumps_parallel = MT_DUMPS_PARALLEL_DEFAULT; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
     bool summaries_parallel = MT_SUMMARIES_PARALLEL_DEFAULT; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
+    bool tiles_parallel = MT_TILES_PARALLEL_DEFAULT; /* k_find_tiles' / k_stacks' walk (MT_VAR_TILES_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
@@ -1089,6 +1148,13 @@ struct ProfOps {
     int32_t (*summary_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, int64_t* dsize);
     int32_t (*summaries)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t mode, const int64_t* doff,
                          uint8_t* dout, bool par);
+    /* the marker queries: dset = the label's value bitmap (1,024 words) on the device */
+    int32_t (*find_tiles)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key, const uint32_t* dset,
+                          int32_t* dout, int32_t* dstatus, bool par);
+    int32_t (*stack_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key, const uint32_t* dset,
+                           int32_t* dcount, int64_t* dhigh, int32_t* dstatus);
+    int32_t (*stacks)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key, const uint32_t* dset,
+                      const int64_t* doff, int32_t* dout, bool par);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1228,9 +1294,35 @@ struct Launch {
                                doff, dout);
         return launch_check(e, "k_summaries");
     }
+    static int32_t find_tiles(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key,
+                              const uint32_t* dset, int32_t* dout, int32_t* dstatus, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_find_tiles<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, key,
+                               dset, dout, dstatus);
+        else
+            hipLaunchKernelGGL((k_find_tiles<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, key,
+                               dset, dout, dstatus);
+        return launch_check(e, "k_find_tiles");
+    }
+    static int32_t stack_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key,
+                               const uint32_t* dset, int32_t* dcount, int64_t* dhigh, int32_t* dstatus) {
+        hipLaunchKernelGGL((k_stack_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, key, dset,
+                           dcount, dhigh, dstatus);
+        return launch_check(e, "k_stack_sizes");
+    }
+    static int32_t stacks(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key, const uint32_t* dset,
+                          const int64_t* doff, int32_t* dout, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_stacks<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, key, dset,
+                               doff, dout);
+        else
+            hipLaunchKernelGGL((k_stacks<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, key, dset,
+                               doff, dout);
+        return launch_check(e, "k_stacks");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
         return ProfOps{init,   start_collab, replay, hdr,     digest,     dump,  length, text,       seg,
                        refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps,
-                       summary_sizes, summaries};
+                       summary_sizes, summaries, find_tiles, stack_sizes, stacks};
     }
 };

@@ -874,6 +874,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value != 0 && value != 1) return MT_E_ARG;
         e->summaries_parallel = value == 1;
         return MT_OK;
+    case MT_VAR_TILES_PARALLEL:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->tiles_parallel = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1330,6 +1334,93 @@ int64_t mt_engine_summaries(mt_engine* e, int64_t m, const int64_t* docs, int32_
         [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, const int64_t* doff, uint8_t* dout) {
             return x->ops->summaries(x, s, n, q, mode, doff, dout, par);
         });
+}
+
+/* ---- batched marker queries (mt_kernels.h k_find_tiles / k_stack_sizes / k_stacks) ----
+ * The label's value bitmap is copied once per call, into the root engine's read buffer (every engine of a chain is on
+ * the root's device). */
+int32_t mt_engine_find_tiles(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, const int32_t* preceding,
+                             int32_t label_key, const uint32_t* value_set, mt_tile_ref* out, int32_t* status_out) {
+    if (!e || m < 0) return MT_E_ARG;
+    if (m == 0) return MT_OK;
+    if (!out || !status_out || !value_set) return MT_E_ARG;
+    ReadPlan p;
+    /* a missing pos is undefined (-1) for every query; a missing preceding takes the same default, and any value
+     * but 0 means preceding */
+    int32_t rc = read_plan(e, m, docs, pos, preceding, -1, nullptr, nullptr, p);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), vb = 4 * (size_t)MT_LABEL_SET_WORDS,
+                 rb = up16(4 * (size_t)m * MT_TILE_WORDS);
+    if ((rc = ensure(e, e->rq, qb + vb + rb + 4 * (size_t)m))) return rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    uint32_t* dset = (uint32_t*)(base + qb);
+    int32_t* dres = (int32_t*)(base + qb + vb);
+    int32_t* dst = (int32_t*)(base + qb + vb + rb);
+    HIPCHK(e, hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(dset, value_set, vb, hipMemcpyHostToDevice, e->stream));
+    const bool par = e->tiles_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->find_tiles(x, s, n, q, label_key, dset, dres, dst, par);
+    });
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(out, dres, 4 * (size_t)m * MT_TILE_WORDS, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MT_OK;
+}
+
+int64_t mt_engine_stack_contexts(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, int32_t label_key,
+                                 const uint32_t* value_set, int64_t* off_out, int32_t* count_out, int32_t* status_out,
+                                 mt_tile_ref* out, int64_t cap) {
+    if (!e || m < 0 || cap < 0) return -MT_E_ARG;
+    if (m == 0) return 0;
+    if (!off_out || !count_out || !status_out || !value_set) return -MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, pos, nullptr, -1, nullptr, nullptr, p);
+    if (rc) return -rc;
+    if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
+    /* the queries, the label set, the high-water marks, the offsets, the counts, the statuses */
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), vb = 4 * (size_t)MT_LABEL_SET_WORDS, sb = up16(8 * (size_t)m),
+                 ob = up16(8 * ((size_t)m + 1)), cb = up16(4 * (size_t)m);
+    if ((rc = ensure(e, e->rq, qb + vb + sb + ob + 2 * cb))) return -rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    uint32_t* dset = (uint32_t*)(base + qb);
+    int64_t* dhigh = (int64_t*)(base + qb + vb);
+    int64_t* doff = (int64_t*)(base + qb + vb + sb);
+    int32_t* dcount = (int32_t*)(base + qb + vb + sb + ob);
+    int32_t* dst = (int32_t*)(base + qb + vb + sb + ob + cb);
+    if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+        hipMemcpyAsync(dset, value_set, vb, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->stack_sizes(x, s, n, q, label_key, dset, dcount, dhigh, dst);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(off_out + 1, dhigh, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipMemcpyAsync(count_out, dcount, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    off_out[0] = 0;
+    for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
+    const int64_t total = off_out[m];
+    if (!out || total > cap || total == 0) return total; /* all or nothing */
+    const size_t eb = 4 * (size_t)MT_TILE_WORDS;
+    if (ensure(e, e->tmp, eb * (size_t)total)) return -MT_E_NOMEM;
+    int32_t* dout = (int32_t*)e->tmp.p;
+    if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    const bool par = e->tiles_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->stacks(x, s, n, q, label_key, dset, doff, dout, par);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(out, dout, eb * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    return total;
 }
 
 /* k_segs over m queries: res[i * MT_SEGQ_N ..] = query i's words; status_out[i] = MT_E_UNSUPPORTED for a refused one */

@@ -44,6 +44,7 @@ _LIB = None
 MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS, MT_VAR_TEXTS_PACKED = 1, 2, 3, 4  # include/mt_engine.h
 MT_VAR_DUMPS_PARALLEL = 5
 MT_VAR_SUMMARIES_PARALLEL = 6
+MT_VAR_TILES_PARALLEL = 7
 
 
 def lib() -> ctypes.CDLL:
@@ -115,6 +116,9 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_dumps.restype = i64
         L.mt_engine_summaries.argtypes = [vp, i64, vp, i32, vp, vp, i64]
         L.mt_engine_summaries.restype = i64
+        L.mt_engine_find_tiles.argtypes = [vp, i64, vp, vp, vp, i32, vp, vp, vp]
+        L.mt_engine_stack_contexts.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, i64]
+        L.mt_engine_stack_contexts.restype = i64
         L.mt_engine_get_containing_segments.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_resolve_remote_client_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_adjust_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
@@ -440,6 +444,61 @@ class Engine:
         buf, off = self.summaries_raw(docs, legacy)
         raw = buf.tobytes()
         return [raw[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+    # ---- batched marker queries (mt_engine_find_tiles / mt_engine_stack_contexts): the local view ----
+    def _label_query(self, interner, label, key, docs, pos):
+        """(m, docs, positions or None, key id, label set) of one label's queries: pos None = undefined for every
+        query, else one entry per query (a scalar is broadcast; None or a negative entry = undefined)"""
+        m, d, _, _ = self._queries(docs, None, None)
+        p = None
+        if pos is not None:
+            if np.ndim(pos) == 0:
+                pos = [pos] * m
+            p = np.ascontiguousarray([-1 if v is None else int(v) for v in pos], np.int32)
+            if len(p) != m:
+                raise ValueError("one position per query")
+        return m, d, p, interner.key_ids.get(key, 0), np.ascontiguousarray(interner.values_containing(label))
+
+    def find_tiles(self, label: str, docs=None, pos=None, preceding=True, *, interner, key: str = ol.TILE_LABELS_KEY):
+        """Client.findTile(pos, label, preceding) per query (mt_engine_find_tiles), in each replica's local view:
+        (tiles, status). tiles: an array of oplog.TILE_REF (rid -1 where the reference returns undefined; `ordinal`
+        indexes the document's dump records, `pos` is the marker's position); status[i] is 0, or MT_E_UNSUPPORTED
+        when an annotate changed the label key on a marker of the document. `interner` is the one the replayed
+        batch was built with: it names the label key and the arrays that hold the label."""
+        m, d, p, kid, bits = self._label_query(interner, label, key, docs, pos)
+        pre = np.ascontiguousarray(np.broadcast_to(np.asarray(preceding, bool), (m,)).astype(np.int32))
+        out, st = np.zeros(m, ol.TILE_REF), np.zeros(m, np.int32)
+        if m:
+            self._check(self.L.mt_engine_find_tiles(self.h, m, self._pn(d), self._pn(p), _p(pre), kid, _p(bits), _p(out),
+                                                    _p(st)), "find_tiles")
+        return out, st
+
+    def stack_contexts_raw(self, label: str, docs=None, pos=None, *, interner, key: str = ol.RANGE_LABELS_KEY):
+        """mt_engine_stack_contexts as arrays: (entries, off, count, status); query i's stack is
+        entries[off[i]:off[i] + count[i]] (oplog.TILE_REF, bottom first). One size query and one fill; the fill call sizes
+        again (all or nothing against cap, as get_texts_units), so three launches and the label set copied twice."""
+        m, d, p, kid, bits = self._label_query(interner, label, key, docs, pos)
+        off, cnt, st = np.zeros(m + 1, np.int64), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        if not m:
+            return np.zeros(0, ol.TILE_REF), off, cnt, st
+
+        def call(out, cap):
+            n = self.L.mt_engine_stack_contexts(self.h, m, self._pn(d), self._pn(p), kid, _p(bits), _p(off), _p(cnt),
+                                                _p(st), out, cap)
+            if n < 0:
+                raise EngineError(f"stack_contexts failed {n}", -n)
+            return n
+        n = call(None, 0)
+        buf = np.zeros(max(n, 1), ol.TILE_REF)
+        if n and call(_p(buf), n) != n:
+            raise EngineError("stack_contexts size changed")
+        return buf[:n], off, cnt, st
+
+    def stack_contexts(self, label: str, docs=None, pos=None, *, interner, key: str = ol.RANGE_LABELS_KEY):
+        """Client.getStackContext(pos, [label])[label] per query (mt_engine_stack_contexts): (list of TILE_REF
+        arrays, bottom first; status as find_tiles)."""
+        buf, off, cnt, st = self.stack_contexts_raw(label, docs, pos, interner=interner, key=key)
+        return [buf[off[i]:off[i] + cnt[i]].copy() for i in range(len(cnt))], st
 
     def _positions(self, fn, what, pos, docs, seqs, long_clients):
         m, d, rs, lc = self._queries(docs, seqs, long_clients)

@@ -87,12 +87,19 @@ export interface DeltaEvent {
     deltaSegments: Array<{ position?: number; length: number; opType?: number; propertyDeltas?: PropertySet }>;
 }
 
+/** a marker a tile / stack query found: its handle, its index in segments(), its local position, its refType */
+export interface TileRef { rid: number; gen: number; ordinal: number; pos: number; refType: number; }
+
 export declare class Interner {
     key(k: string): number;
     value(v: unknown): number;
     /** a SubSequence item's id (the units of a SubSequence row) and back */
     item(v: unknown): number;
     itemObj(i: number): unknown;
+    /** the label set of a marker query: a bitmap over the value ids, bit v set when value v is an array holding label */
+    valuesContaining(label: string): Uint32Array;
+    /** the id of a key the interner has seen, else 0 */
+    knownKey(k: string): number;
 }
 
 export declare function decodeDeltas(words: Int32Array, interner: Interner): DeltaEvent[];
@@ -121,6 +128,11 @@ export declare class ReplayEngine {
     /** the summary dump of every listed document (default: all): the segments SnapshotV1.extractSync (or, with
      *  legacy, SnapshotLegacy.extractSync) yields, extracted on the device (mt_engine_summaries); decodeDump reads it */
     summaries(docs?: number[], options?: { legacy?: boolean }): Buffer[];
+    /** Client.findTile for many replicas in one launch (mt_engine_find_tiles): undefined where the reference returns
+     *  undefined; {unsupported: true} when an annotate changed referenceTileLabels on a marker of the document */
+    findTiles(queries: { doc: number; pos?: number; preceding?: boolean }[], label: string): (TileRef | { unsupported: true } | undefined)[];
+    /** Client.getStackContext(pos, [label])[label] for many replicas (mt_engine_stack_contexts): bottom first */
+    stackContexts(queries: { doc: number; pos?: number }[], label: string): (TileRef[] | { unsupported: true })[];
     longIndex(name: string): number;
 }
 
@@ -200,6 +212,8 @@ export declare class GpuClient {
     insertSegmentLocal(pos: number, spec: SegmentSpec | [number, number]): MergeTreeOp | undefined;
     /** Client.findTile (client.ts:1075-1078): the nearest Tile marker with the label, preceding startPos or after it */
     findTile(startPos: number | undefined, tileLabel: string, preceding?: boolean): { tile: SegmentObject; pos: number } | undefined;
+    /** Client.getStackContext (client.ts:948): per asked label the open NestBegin / NestEnd markers, bottom first */
+    getStackContext(startPos: number | undefined, rangeLabels: string[]): { [label: string]: SegmentObject[] };
     /** Client.getMarkerFromId (client.ts:312) */
     getMarkerFromId(id: string): SegmentObject | undefined;
     /** Client.annotateMarker (client.ts:143-154): the op with relative positions, or undefined */

@@ -32,6 +32,9 @@ const UnassignedSequenceNumber = -1;
 const ReferenceType = { Simple: 0x0, Tile: 0x1, NestBegin: 0x2, NestEnd: 0x4, SlideOnRemove: 0x40 }; // ops.ts:6-15
 const NOOP_SPLIT = 1; // seg_kind of a local NOOP record: walkSegments' splitRange (mt_oplog.h MT_NOOP_SPLIT)
 const TILE_LABELS_KEY = "referenceTileLabels"; // reservedTileLabelsKey (mergeTree.ts:615)
+const RANGE_LABELS_KEY = "referenceRangeLabels"; // reservedRangeLabelsKey (mergeTree.ts:616)
+const LABEL_SET_WORDS = 1024, TILE_WORDS = 5; // MT_LABEL_SET_WORDS, MT_TILE_WORDS (include/mt_engine.h)
+const E_UNSUPPORTED = 4; // MT_E_UNSUPPORTED
 const HANDLE_UNALLOCATED = -0x80000000; // Handle.unallocated (matrix handletable.ts:11)
 const SEG = { TEXT: 0, MARKER: 1, PERM: 2, RUN: 3 }; // RUN: SubSequence items (mt_oplog.h MT_SEG_RUN)
 const SEG_RELPOS = 0x80; // positions relative to markers (mt_oplog.h MT_SEG_RELPOS)
@@ -83,6 +86,19 @@ class Interner {
         const falsy = typeof v !== "object" && !v;
         return i | (falsy ? VALUE_FALSY : 0);
     }
+    /* the label set of a marker query (mt_engine.h mt_engine_find_tiles): a bitmap over the 2^15 value ids, bit v set
+     * when value v is an array that contains `label` (a label no interned array holds: all zero) */
+    valuesContaining(label) {
+        const bits = new Uint32Array(LABEL_SET_WORDS);
+        for (const [sv, i] of this.values) {
+            if (sv[0] !== "[") continue;
+            const v = JSON.parse(sv);
+            if (Array.isArray(v) && v.includes(label)) bits[i >> 5] |= 1 << (i & 31);
+        }
+        return bits;
+    }
+    /* the id of a key the interner has seen, else 0 (which no property holds) */
+    knownKey(k) { const i = this.keys.get(k); return i === undefined ? 0 : i; }
     /* include/mt_oplog.h MT_VKIND_* per value id (mt_engine_set_value_kinds): what an incr annotate makes of it */
     kinds() {
         const k = new Uint8Array(this.nv);
@@ -415,6 +431,43 @@ class ReplayEngine {
         const { data, offsets } = addon.summaries(this.h, docs, !!(options && options.legacy));
         return Array.from({ length: offsets.length - 1 }, (_, i) => data.subarray(offsets[i], offsets[i + 1]));
     }
+
+    /* Client.findTile(pos, label, preceding) for many replicas in one launch (mt_engine_find_tiles): queries is an array
+     * of {doc, pos (undefined allowed), preceding (default true)}; the answer per query is {ordinal, pos, refType, rid,
+     * gen} (ordinal: the marker's index in its document's segments()), undefined where the reference returns undefined,
+     * or {unsupported: true} when an annotate changed referenceTileLabels on a marker of the document */
+    findTiles(queries, label) {
+        this.flush();
+        const docs = queries.map((q) => q.doc);
+        checkDocs(this, docs);
+        const pos = Int32Array.from(queries, (q) => (q.pos === undefined || q.pos === null ? -1 : q.pos));
+        const pre = Int32Array.from(queries, (q) => (q.preceding === false ? 0 : 1));
+        const [t, st] = addon.findTiles(this.h, docs, pos, pre, this.interner.knownKey(TILE_LABELS_KEY),
+            this.interner.valuesContaining(label));
+        return queries.map((_, i) => (st[i] === E_UNSUPPORTED ? { unsupported: true } : tileOf(t, i)));
+    }
+
+    /* Client.getStackContext(pos, [label])[label] for many replicas (mt_engine_stack_contexts: a size query and a fill,
+     * three launches, the fill call sizing again as mt_engine_get_texts' does): queries is
+     * an array of {doc, pos}; the answer per query is the stack, bottom first, of entries as findTiles', or
+     * {unsupported: true} */
+    stackContexts(queries, label) {
+        this.flush();
+        const docs = queries.map((q) => q.doc);
+        checkDocs(this, docs);
+        const pos = Int32Array.from(queries, (q) => (q.pos === undefined || q.pos === null ? -1 : q.pos));
+        const r = addon.stackContexts(this.h, docs, pos, this.interner.knownKey(RANGE_LABELS_KEY),
+            this.interner.valuesContaining(label));
+        return queries.map((_, i) => (r.status[i] === E_UNSUPPORTED ? { unsupported: true }
+            : Array.from({ length: r.counts[i] }, (_x, k) => tileOf(r.entries, r.offsets[i] + k))));
+    }
+}
+
+/* entry i of a marker-query result (MT_TILE_WORDS words: rid, gen, ordinal, position, refType) */
+function tileOf(words, i) {
+    const o = i * TILE_WORDS;
+    if (words[o] < 0) return undefined;
+    return { rid: words[o], gen: words[o + 1], ordinal: words[o + 2], pos: words[o + 3], refType: words[o + 4] };
 }
 
 /* the latched errors of the listed documents (undefined: all), read in one call */
@@ -766,6 +819,18 @@ class GpuClient {
      * markers of non-zero local length (addNodeReferences 262-300), the segment the search stops at counts as it
      * is (backwardSearch from the document's end stops at its last segment, whatever its length). */
     findTile(startPos, tileLabel, preceding = true) {
+        /* one device query (mt_engine_find_tiles) decides the tile; the dump walk below only where the engine refuses
+         * (an annotate changed the label key on a marker), so that every answer stays what it was. The tile is handed
+         * out as a segments() object, so a replica whose dump is not decoded yet still pays for the dump: only
+         * ReplayEngine.findTiles, which returns ordinals and positions, does without it. */
+        this.read();
+        const [r] = this.engine.findTiles([{ doc: this.doc, pos: startPos, preceding }], tileLabel);
+        if (r === undefined) return undefined;
+        if (!r.unsupported) return { tile: this.segments().segments[r.ordinal], pos: r.pos };
+        return this._findTileByDump(startPos, tileLabel, preceding);
+    }
+
+    _findTileByDump(startPos, tileLabel, preceding) {
         const d = this.segments();
         const segs = d.segments;
         const ok = (seg) => seg.len > 0 && hasTileLabel(seg, tileLabel);
@@ -786,6 +851,22 @@ class GpuClient {
         }
         if (stop >= 0 && hasTileLabel(segs[stop], tileLabel)) tile = segs[stop];
         return tile === undefined ? undefined : { tile, pos: tile.pos };
+    }
+
+    /* Client.getStackContext(startPos, rangeLabels) (client.ts:948 -> MergeTree.getStackContext, mergeTree.ts:1783-1793):
+     * per label that has a stack, the NestBegin / NestEnd markers open at startPos, bottom first, as segments()
+     * objects; one device call per label (mt_engine_stack_contexts). Every asked label has an entry, an empty array where
+     * the reference's map holds an empty stack or none. A label key an annotate changed on a marker throws. */
+    getStackContext(startPos, rangeLabels) {
+        this.read();
+        const segs = this.segments().segments;
+        const out = {};
+        for (const label of rangeLabels) {
+            const [st] = this.engine.stackContexts([{ doc: this.doc, pos: startPos }], label);
+            if (st.unsupported) throw new Error("getStackContext: unsupported (referenceRangeLabels was annotated on a marker)");
+            out[label] = st.map((e) => segs[e.ordinal]);
+        }
+        return out;
     }
 
     /* Client.getMarkerFromId (client.ts:312-314; mergeTree.ts:1965-1967): the marker whose markerId is id, as a

@@ -748,6 +748,82 @@ static napi_value js_adjust_positions(napi_env env, napi_callback_info info) {
     return res;
 }
 
+/* findTiles(h, docs, pos, preceding, keyId, valueSet) -> [Int32Array tiles, Int32Array status]: Client.findTile per
+ * query in the local view (mt_engine_find_tiles). docs is an array of document ids; pos and preceding are Int32Arrays of
+ * its length (pos < 0: undefined); valueSet is the label's Uint32Array of MT_LABEL_SET_WORDS words; tiles holds
+ * MT_TILE_WORDS words per query: rid (-1: none), gen, ordinal, position, refType */
+static napi_value js_find_tiles(napi_env env, napi_callback_info info) {
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = false;
+    if (!e || !docs_of(env, argv[1], &docs, &all)) return nullptr;
+    void *pp, *pr, *ps;
+    size_t lp, lr, ls;
+    int32_t key;
+    if (!view_of(env, argv[2], &pp, &lp, napi_int32_array) || !view_of(env, argv[3], &pr, &lr, napi_int32_array) ||
+        !i32_of(env, argv[4], &key) || !view_of(env, argv[5], &ps, &ls, napi_uint32_array))
+        return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (lp != m || lr != m || ls != MT_LABEL_SET_WORDS) return throw_status(env, e, MT_E_ARG, "findTiles (array lengths)");
+    std::vector<mt_tile_ref> out(m + 1);
+    std::vector<int32_t> st(m + 1, 0);
+    int32_t rc = mt_engine_find_tiles(e, (int64_t)m, all ? nullptr : docs.data(), (const int32_t*)pp, (const int32_t*)pr,
+                                      key, (const uint32_t*)ps, out.data(), st.data());
+    if (rc) return throw_status(env, e, rc, "mt_engine_find_tiles");
+    napi_value res, a = i32_array(env, (const int32_t*)out.data(), m * MT_TILE_WORDS), b = i32_array(env, st.data(), m);
+    if (!a || !b) return nullptr;
+    NAPI_OK(napi_create_array_with_length(env, 2, &res));
+    NAPI_OK(napi_set_element(env, res, 0, a));
+    NAPI_OK(napi_set_element(env, res, 1, b));
+    return res;
+}
+
+/* stackContexts(h, docs, pos, keyId, valueSet) -> {entries: Int32Array, offsets: number[], counts: Int32Array, status:
+ * Int32Array}: Client.getStackContext for one label per query (mt_engine_stack_contexts: a size query and a fill that
+ * sizes again, so three launches and the label set copied twice, as getTexts); query
+ * i's stack is the first counts[i] entries (MT_TILE_WORDS words each, bottom first) from entry offsets[i] on */
+static napi_value js_stack_contexts(napi_env env, napi_callback_info info) {
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = false;
+    if (!e || !docs_of(env, argv[1], &docs, &all)) return nullptr;
+    void *pp, *ps;
+    size_t lp, ls;
+    int32_t key;
+    if (!view_of(env, argv[2], &pp, &lp, napi_int32_array) || !i32_of(env, argv[3], &key) ||
+        !view_of(env, argv[4], &ps, &ls, napi_uint32_array))
+        return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (lp != m || ls != MT_LABEL_SET_WORDS) return throw_status(env, e, MT_E_ARG, "stackContexts (array lengths)");
+    const int64_t* dp = all ? nullptr : docs.data();
+    std::vector<int64_t> off(m + 1, 0);
+    std::vector<int32_t> cnt(m + 1, 0), st(m + 1, 0);
+    int64_t n = mt_engine_stack_contexts(e, (int64_t)m, dp, (const int32_t*)pp, key, (const uint32_t*)ps, off.data(),
+                                         cnt.data(), st.data(), nullptr, 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_stack_contexts");
+    std::vector<mt_tile_ref> buf((size_t)n + 1);
+    if (n > 0) {
+        int64_t n2 = mt_engine_stack_contexts(e, (int64_t)m, dp, (const int32_t*)pp, key, (const uint32_t*)ps, off.data(),
+                                              cnt.data(), st.data(), buf.data(), n);
+        if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_stack_contexts");
+    }
+    napi_value out, offs, a = i32_array(env, (const int32_t*)buf.data(), (size_t)n * MT_TILE_WORDS),
+                          b = i32_array(env, cnt.data(), m), c = i32_array(env, st.data(), m);
+    if (!a || !b || !c) return nullptr;
+    NAPI_OK(napi_create_array_with_length(env, m + 1, &offs));
+    for (size_t i = 0; i <= m; i++) NAPI_OK(napi_set_element(env, offs, (uint32_t)i, num(env, (double)off[i])));
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "entries", a));
+    NAPI_OK(napi_set_named_property(env, out, "offsets", offs));
+    NAPI_OK(napi_set_named_property(env, out, "counts", b));
+    NAPI_OK(napi_set_named_property(env, out, "status", c));
+    return out;
+}
+
 /* handleToPosition(h, doc, handle, localSeq) -> number */
 static napi_value js_handle_to_position(napi_env env, napi_callback_info info) {
     napi_value argv[4];
@@ -843,7 +919,8 @@ static napi_value init(napi_env env, napi_value exports) {
                {"dump", js_dump},           {"segmentIds", js_segment_ids},
                {"submitDocs", js_submit_docs}, {"docError", js_doc_error}, {"setValueKinds", js_set_value_kinds},
                {"getLengths", js_get_lengths}, {"getTexts", js_get_texts}, {"adjustPositions", js_adjust_positions},
-               {"dumps", js_dumps},         {"summaries", js_summaries}};
+               {"dumps", js_dumps},         {"summaries", js_summaries},
+               {"findTiles", js_find_tiles}, {"stackContexts", js_stack_contexts}};
     for (auto& f : fns) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.cb, nullptr, &fn));

@@ -62,6 +62,13 @@ def _falsy(v: Any) -> bool:
     return v is not None and not v and not isinstance(v, (dict, list))
 
 
+LABEL_SET_WORDS = 1024  # MT_LABEL_SET_WORDS (include/mt_engine.h): 2^15 value ids, a bit each
+TILE_LABELS_KEY, RANGE_LABELS_KEY = "referenceTileLabels", "referenceRangeLabels"  # mergeTree.ts:615-616
+REF_TILE, REF_NEST_BEGIN, REF_NEST_END = 1, 2, 4  # ReferenceType (ops.ts:6-15)
+# mt_tile_ref (include/mt_engine.h): a marker a tile / stack query found; rid -1 = none
+TILE_REF = np.dtype([("rid", "<i4"), ("gen", "<i4"), ("ordinal", "<i4"), ("pos", "<i4"), ("ref_type", "<i4")])
+
+
 class Interner:
     """Batch-global key / value string tables. Value id 0 is JSON null (= delete). `items`: SubSequence items
     (mt_oplog.h MT_SEG_RUN) by canonical JSON, ids 0..65535: what a SubSequence row's units hold."""
@@ -110,6 +117,18 @@ class Interner:
             self.values.append(s)
             self.value_ids[s] = i
         return i | (VALUE_FALSY if _falsy(v) else 0)
+
+    def values_containing(self, label: str) -> np.ndarray:
+        """The label set of a marker query (mt_engine.h mt_engine_find_tiles): a bitmap over the 2^15 value ids, 1,024
+        uint32 words, bit v set when value v is an array that contains `label` (referenceTileLabels /
+        referenceRangeLabels values are arrays of strings, interned whole). A label no array holds: all zero."""
+        bits = np.zeros(LABEL_SET_WORDS, np.uint32)
+        for i, sv in enumerate(self.values):
+            if i and sv.startswith("["):
+                v = json.loads(sv)
+                if isinstance(v, list) and label in v:
+                    bits[i >> 5] |= np.uint32(1 << (i & 31))
+        return bits
 
     def key_str(self, i: int) -> str:
         return self.keys[i]

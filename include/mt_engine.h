@@ -143,9 +143,12 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *   MT_VAR_SUMMARIES_PARALLEL (0 | 1): how mt_engine_summaries' fill kernel writes: 1 = the wave decides a pass of 64
  *     rows at once, every run head and window row writes its own record and the wave copies the texts together,
  *     0 = one lane walks the rows and writes (the host core's writer); takes effect at the next mt_engine_summaries.
+ *   MT_VAR_TILES_PARALLEL (0 | 1): how mt_engine_find_tiles and mt_engine_stack_contexts walk: 1 = the wave classifies a
+ *     pass of 64 rows at once, 0 = the serial walk of the host core (a second device check, and the A/B baseline);
+ *     takes effect at the next such call.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
 enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4,
-       MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6 };
+       MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6, MT_VAR_TILES_PARALLEL = 7 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -266,6 +269,39 @@ int64_t mt_engine_dumps(mt_engine* e, int64_t m, const int64_t* docs, int64_t* o
  * out == NULL is the size query; m == 0 returns 0 and touches nothing. */
 int64_t mt_engine_summaries(mt_engine* e, int64_t m, const int64_t* docs, int32_t mode, int64_t* off_out, uint8_t* out,
                             int64_t cap);
+/* ---- batched marker queries: the local view only (Client.findTile and Client.getStackContext always ask as the
+ * replica's own client under UniversalSequenceNumber), so there is no perspective and none is refused for one.
+ * A label is a string inside an array-valued property (referenceTileLabels / referenceRangeLabels), which the host
+ * interns as one value id; the device holds no strings. A call carries one label: label_key is the interned key, and
+ * value_set a bitmap over the 2^15 host value ids (MT_LABEL_SET_WORDS words), bit v set when value v is an array that
+ * holds the label (values the engine derives are never arrays and never match). docs == NULL: documents 0..m-1;
+ * documents may repeat, in any order; pos[i] < 0 (or pos == NULL) is an undefined position. status_out[i] (required)
+ * is MT_OK, or MT_E_UNSUPPORTED when an annotate changed label_key on a marker of the document: the reference's block
+ * caches are then stale in a way that depends on its block-update history (as mt_engine_get_marker_from_id). Tiles and
+ * range labels on local references (hierRefCount, mergeTree.ts:294-307) are not modelled. */
+#define MT_LABEL_SET_WORDS 1024
+#define MT_TILE_WORDS 5
+typedef struct mt_tile_ref {
+    int32_t rid;      /* row id of the marker, -1: none (or a refused query) */
+    int32_t gen;      /* row-id generation (a handle, as mt_seg_ref) */
+    int32_t ordinal;  /* the marker's index in walkAllSegments order (its canonical dump record) */
+    int32_t pos;      /* its position in the local view (MergeTree.getPosition) */
+    int32_t ref_type; /* its ReferenceType bits (ops.ts:6-15) */
+} mt_tile_ref;
+/* Client.findTile(startPos, tileLabel, preceding) (client.ts:1075-1078 -> MergeTree.findTile, mergeTree.ts:1796-1822)
+ * per query: the nearest marker with the Tile refType and the label, at or before pos[i] (preceding[i] != 0; preceding
+ * == NULL: every query) or at or after it; out[i].rid = -1 where the reference returns undefined. */
+int32_t mt_engine_find_tiles(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, const int32_t* preceding,
+                             int32_t label_key, const uint32_t* value_set, mt_tile_ref* out, int32_t* status_out);
+/* Client.getStackContext(startPos, [rangeLabel]) (client.ts:948 -> MergeTree.getStackContext, mergeTree.ts:1783-1793)
+ * per query: the stack of NestBegin / NestEnd markers with the label that are open at pos[i], bottom first. Works like
+ * mt_engine_get_texts: off_out[0..m] is always filled, query i's window is out[off_out[i] .. off_out[i+1]) entries,
+ * sized by the deepest the walk gets, and its first count_out[i] entries are the answer; returns the total entry count
+ * (<0: -MT_E_*); `out` is written only when the total fits cap (all or nothing); out == NULL is the size query (one
+ * launch); a call with `out` sizes and then fills (two launches); the label set is copied once per call. */
+int64_t mt_engine_stack_contexts(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos, int32_t label_key,
+                                 const uint32_t* value_set, int64_t* off_out, int32_t* count_out, int32_t* status_out,
+                                 mt_tile_ref* out, int64_t cap);
 /* MergeTree.getContainingSegment(pos, refSeq, clientId) (mergeTree.ts:1656-1667) per query; out[i].rid = -1
  * where there is no segment at pos[i]. */
 int32_t mt_engine_get_containing_segments(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* pos,

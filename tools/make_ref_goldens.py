@@ -549,6 +549,56 @@ def make_inserts(node: str) -> None:
           f"census {cen}; {len(keep)} whole dumps; {len(load_msgs)} summaries do not load", flush=True)
 
 
+def make_tiles(node: str) -> None:
+    """tests/golden/reftiles.npz: the hand-built marker-query cases (tests/tile_logs.py) replayed by the reference, and
+    the reference Client's own answers to each case's queries: Client.findTile as (found, pos, the tile's index in
+    walkAllSegments order) and Client.getStackContext per label as the stack's (index, refType) pairs, bottom first.
+    Every case's witness must hold on the reference's dump, which the fixture keeps whole."""
+    import tile_logs as tl
+    import oracle_client as oc
+    cs = tl.cases()
+    b = tl.batch(cs)
+    it = tl.interner()
+    tq, sq = tl.queries(cs)
+    d = os.path.join(SCRATCH, "tiles")
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "tilequeries.json"), "w") as f:
+        json.dump({"tiles": [list(q) for q in tq], "stacks": [list(q) for q in sq]}, f)
+    dumps, info, secs, _ = run_reference(b, d, node, interner=it)
+    parsed = [ol.parse_dump(x) for x in dumps]
+    for c, p in zip(cs, parsed):
+        if not c.witness(*p):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump")
+    digests = np.asarray([fnv1a64(x) for x in dumps], np.uint64)
+    _, odig, oerr = oc.replay_batch(b)
+    if not ((odig == digests).all() and (oerr == 0).all()):
+        raise RuntimeError(f"the oracle differs from the reference on {[c.name for c, a, r in zip(cs, odig, digests) if a != r]}")
+    ans = json.load(open(os.path.join(d, "ref_tiles.json")))
+    assert len(ans["tiles"]) == len(tq) and len(ans["stacks"]) == len(sq)
+    flat = [x for st in ans["stacks"] for x in st]
+    keep = [i for i, p in enumerate(parsed) if p[0]["nsegs"] < 400]
+    np.savez_compressed(
+        os.path.join(GOLDEN, "reftiles.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=digests, nrows=np.asarray([p[0]["nsegs"] for p in parsed], np.int64),
+        keep=np.asarray(keep, np.int64), dumps=np.frombuffer(b"".join(dumps[i] for i in keep), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(dumps[i]) for i in keep])]).astype(np.int64),
+        tile_doc=np.asarray([q[0] for q in tq], np.int32), tile_label=np.asarray([q[1] for q in tq]),
+        tile_pos=np.asarray([-1 if q[2] is None else q[2] for q in tq], np.int32),
+        tile_preceding=np.asarray([q[3] for q in tq], bool),
+        tile_answers=np.asarray(ans["tiles"], np.int32).reshape(-1, 3),
+        stack_doc=np.asarray([q[0] for q in sq], np.int32), stack_label=np.asarray([q[1] for q in sq]),
+        stack_pos=np.asarray([-1 if q[2] is None else q[2] for q in sq], np.int32),
+        stack_off=np.concatenate([[0], np.cumsum([len(st) for st in ans["stacks"]])]).astype(np.int64),
+        stack_entries=np.asarray(flat, np.int32).reshape(-1, 2),
+        source=("packages/dds/merge-tree/src (reference, type-erased by tools/ts_erase.py) under node by "
+                "tools/ref_replay.mjs with tilequeries.json: Client.findTile / Client.getStackContext after each "
+                "document's replay; logs: tests/tile_logs.py"))
+    nf = int(sum(a[0] for a in ans["tiles"]))
+    print(f"reftiles: {b.ndocs} docs, {b.nops} records, every witness holds, the oracle agrees on every digest; "
+          f"{len(tq)} findTile queries ({nf} found), {len(sq)} getStackContext queries (deepest "
+          f"{max((len(st) for st in ans['stacks']), default=0)}); {len(keep)} whole dumps", flush=True)
+
+
 def make_props(node: str) -> None:
     """tests/golden/refprops.npz: the hand-built property-manager cases (tests/prop_logs.py: key slots and op widths,
     pending-key counts, rewrites, combining ops, zamboni over 24 keys, the cap cases) replayed by the reference: per
@@ -1280,6 +1330,7 @@ def main() -> None:
     ap.add_argument("--ranges", action="store_true", help="write the wide range-edit fixture (refranges.npz) only")
     ap.add_argument("--reconnect", action="store_true", help="write the hand-built reconnect fixture (refreconnect.npz) only")
     ap.add_argument("--inserts", action="store_true", help="write the insert placement / split fixture (refinserts.npz) only")
+    ap.add_argument("--tiles", action="store_true", help="write the marker-query fixture (reftiles.npz) only")
     ap.add_argument("--props", action="store_true", help="write the property-manager fixture (refprops.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
@@ -1298,6 +1349,9 @@ def main() -> None:
         return
     if args.inserts:
         make_inserts(args.node)
+        return
+    if args.tiles:
+        make_tiles(args.node)
         return
     if args.props:
         make_props(args.node)

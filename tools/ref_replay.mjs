@@ -669,6 +669,18 @@ function getItems(client, start, end) {
     if (end !== undefined) out.splice(end - start);
     return out;
 }
+// optional marker queries (tilequeries.json: {tiles: [[doc, label, pos | null, preceding], ...], stacks: [[doc, label,
+// pos | null], ...]}; null = undefined) after the doc's replay -> ref_tiles.json: Client.findTile (client.ts:1075) as
+// [found, pos, the tile's index in walkAllSegments order]; Client.getStackContext(pos, [label])[label] (client.ts:948)
+// as [[index, refType], ...], bottom first
+const mqpath = path.join(dir, "tilequeries.json");
+const markerQueries = fs.existsSync(mqpath) ? JSON.parse(fs.readFileSync(mqpath)) : { tiles: [], stacks: [] };
+const tileAnswers = [], stackAnswers = [];
+function allSegments(client) {
+    const segs = [];
+    client.mergeTree.walkAllSegments(client.mergeTree.root, (seg) => { segs.push(seg); return true; });
+    return segs;
+}
 const t0 = process.hrtime.bigint();
 const dumps = [], errs = {};
 for (let d = 0; d < ndocs; d++) {
@@ -716,6 +728,19 @@ for (let d = 0; d < ndocs; d++) {
         for (const [qd, st, en] of itemQueries) {
             if (qd !== d) continue;
             itemAnswers.push(getItems(c, st, en === null ? undefined : en).map(itemUnit));
+        }
+        if (markerQueries.tiles.some((q) => q[0] === d) || markerQueries.stacks.some((q) => q[0] === d)) {
+            const segs = allSegments(c);
+            for (const [qd, label, pos, preceding] of markerQueries.tiles) {
+                if (qd !== d) continue;
+                const r = c.findTile(pos === null ? undefined : pos, label, preceding);
+                tileAnswers.push(r === undefined ? [0, -1, -1] : [1, r.pos, segs.indexOf(r.tile)]);
+            }
+            for (const [qd, label, pos] of markerQueries.stacks) {
+                if (qd !== d) continue;
+                const st = c.getStackContext(pos === null ? undefined : pos, [label])[label];
+                stackAnswers.push(st === undefined ? [] : st.items.map((m) => [segs.indexOf(m), m.refType]));
+            }
         }
         for (const [qd, id, before, offset] of relQueries) {
             if (qd !== d) continue;
@@ -823,6 +848,9 @@ if (withHandles) {
     fs.writeFileSync(path.join(dir, "ref_handles.json"), JSON.stringify(snap));
 }
 if (relQueries.length) fs.writeFileSync(path.join(dir, "ref_relpos.json"), JSON.stringify(relAnswers));
+if (markerQueries.tiles.length || markerQueries.stacks.length) {
+    fs.writeFileSync(path.join(dir, "ref_tiles.json"), JSON.stringify({ tiles: tileAnswers, stacks: stackAnswers }));
+}
 if (combineWatch) fs.writeFileSync(path.join(dir, "ref_combine.json"), JSON.stringify(combineAt));
 console.log(JSON.stringify({ ndocs, errors: Object.keys(errs).length, seconds: secs, removeThrew }));
 }
