@@ -507,21 +507,16 @@ struct ProfScope { /* no live register across the scope: the LDS counter takes -
 /* LOAD: applies snapshot-load records (mt_oplog.h MT_OP_RELOAD / COLLAB / APPEND); the plain config-2/3 replay
  * kernel is built without them (its scalar registers: SGPR spills 1,321 -> 1,041, +2.2 % on config 3, r04s) and
  * the engine runs a batch that holds any with the full build */
-/* NARROW: the tiled kernel's variant that keeps the zamboni heap in LDS beside a narrower window set (MT_NARROW_H /
- * MT_NARROW_W entries, mt_kernels.h k_replay_tiled); a document that outgrows either latches E_CAPACITY and replays
+/* NARROW: the tiled kernel's variant that keeps the zamboni heap in LDS beside a narrower window set (NARROW_H /
+ * NARROW_W entries, mt_kernels.h k_replay_tiled); a document that outgrows either latches E_CAPACITY and replays
  * again in the wide variant (capacity promotion, mt_replay.hip) */
-#ifndef MT_NARROW_W
-#define MT_NARROW_W 2048
-#endif
-#ifndef MT_NARROW_H
-#define MT_NARROW_H 2048
-#endif
 template <class W, class HT, bool DL = false, bool LOAD = true, bool NARROW = false>
 struct Replica {
     typedef typename HT::IX IX;
     static constexpr bool TILED = HT::TILED;
-    static constexpr int WCAPR = NARROW ? MT_NARROW_W : HT::TL::WCAP; /* window-set entries */
-    static constexpr int HCAPR = NARROW ? MT_NARROW_H : HT::H;        /* zamboni heap entries */
+    static constexpr int NARROW_W = 2048, NARROW_H = 2048;         /* the NARROW variant's window set and heap */
+    static constexpr int WCAPR = NARROW ? NARROW_W : HT::TL::WCAP; /* window-set entries */
+    static constexpr int HCAPR = NARROW ? NARROW_H : HT::H;        /* zamboni heap entries */
     /* short-id recycling (reclaim_shorts) is built into the larger profiles only: a config-2/3/5 document that meets
      * its 254th client latches E_CAPACITY and replays again in HotMid (capacity promotion, mt_replay.hip), so the
      * small kernels carry none of it */
@@ -575,15 +570,13 @@ struct Replica {
     uint8_t* twgen;
     int32_t* twslot;
     int64_t cur; /* index of the record being applied in the current Pools (snapshot reload reads ahead) */
-    int32_t* pfcur = nullptr; /* tiled kernel: where the prefetch helper waves read `cur` (LDS) */
-    /* tiled kernel built with MT_WIN_HELPER: the LDS mailbox of the second wave that evaluates the window set's second
+    /* tiled kernel: the LDS mailbox of the second wave that evaluates the window set's second
      * block of entries while this wave does the first (win_pass, win_helper) */
     struct WinMail {
-        int32_t req, done, n, refSeq, client, minSeq, local, quit;
+        int32_t n, refSeq, client, minSeq, local, quit;
         int32_t s[64], lc[64], lx[64], len[64], rseq[64], v[64], cp[64], st[64];
     };
     WinMail* wm = nullptr;
-    int32_t wmseq = 0;
     /* an upper bound of every maxSeq in the zamboni heap (INT32_MAX: unknown), set when a replay starts: an
      * entry at or above it cannot move up, so heap_add appends it without reading its ancestors */
     int32_t hmax = INT32_MAX;
@@ -1958,23 +1951,7 @@ struct Replica {
         }
         z.tl.xf[s] = x;
     }
-    /* Evaluate the window set under (refSeq, client): rows the MSN has passed settle into the
-     * STABLE summaries (or DEAD), entries of freed rows drop out, and every remaining row's chunk
-     * position, leaf index and perspective length go to the scratch, its length scattered onto
-     * cdel[chunk position]. Returns the sum of those lengths. */
-#ifndef MT_FIND2
-#define MT_FIND2 1 /* a tiled range op's two ends found in the same passes (tile_find2 / leaf_find2) */
-#endif
-#ifndef MT_WIN_NB
-#define MT_WIN_NB 1 /* wave passes of the window set issued together: 2 covered the ~80-100 rows in one round trip (r04e, 8 -> 2: 8.81 -> 9.66M ops/s at 256 x 300k); since the set's entries and the leaf headers sit in LDS (round 5), one pass at a time is faster (r05zd at 256 x 1M: 2 -> 1: 15.73 -> 15.88M, 4: 14.91M) */
-#endif
-#ifndef MT_WIN_HELPER /* tiled kernel: a second wave of the document's workgroup evaluates the window set's second block
-                          (win_helper) — 2: handed over by two workgroup barriers (r06h at 256 x 300k: 16.21 -> 16.36M
-                          ops/s); 1: by polled LDS flags (r06g: 16.23 -> 15.46M, the s_sleep wake-up costs more than the
-                          global round trip it hides, tools/wave_sync_probe.hip); 0: one wave */
-#define MT_WIN_HELPER 2
-#endif
-    /* stages 1-3 of win_pass for one block of window entries (lane i = b0 + lane < n) under (refSeq, client) with the
+    /* win_pass's evaluation of one block of window entries (lane i = b0 + lane < n) under (refSeq, client) with the
      * given minSeq and local-perspective test: the entry (rd, g), its row's slot s (-1: gone), the row, its leaf's
      * chunk (lc) and index (lx), settle / keep, the perspective length v and the chunk position cp */
     struct WinRow {
@@ -1999,7 +1976,10 @@ struct Replica {
         x.rv = row_view(c);
         x.lc = t.lch[l];
         x.lx = t.lix[l];
-        if (!hit) x.s = gok ? -2 : -1;
+        if (!hit) x.s = gok ? -2 : -1; /* -2: the row moved: leaf, slot, row */
+        /* counted here, where the miss is known; the helper wave's replica has no profile buffer, so the misses
+         * of the block it evaluates are not in the column */
+        MT_PROF_COUNT(PH_C_WMISS, __builtin_popcountll(w.ballot(x.s == -2)));
         if (x.s == -2) {
             int32_t lf = z.RLEAF(x.rd);
             int32_t cc = nch[lf];
@@ -2023,15 +2003,14 @@ struct Replica {
         }
         return x;
     }
-    /* the helper wave's loop (k_replay_tiled with MT_WIN_HELPER): each request of the replaying wave (a window pass
-     * with more than W::N entries) evaluated on the second block, the results left in the mailbox. Exits when the
-     * replaying wave is done (`*quit`). Every wait is bounded. */
-    MT_HD void win_helper(const volatile int32_t* quit) {
+    /* the helper wave's loop (k_replay_tiled): each request of the replaying wave (a window pass
+     * with more than W::N entries) evaluated on the second block, the results left in the mailbox. Every request is two
+     * workgroup barriers, matched by win_pass's pair; the kernel's closing barrier, with `quit` set, ends the loop. */
+    MT_HD void win_helper() {
 #ifdef __HIP_DEVICE_COMPILE__
         if constexpr (TILED && W::N == 64) {
             volatile WinMail* m = wm;
-#if MT_WIN_HELPER == 2
-            for (;;) { /* barrier handoff: every request is two workgroup barriers, matched by win_pass2 */
+            for (;;) {
                 __syncthreads(); /* a request (or the end) is posted */
                 if (m->quit) return;
                 WinRow x = win_block(W::N, m->n, m->refSeq, m->client, m->minSeq, m->local != 0);
@@ -2040,196 +2019,65 @@ struct Replica {
                 m->v[l] = x.v, m->cp[l] = x.cp, m->st[l] = (x.settle ? 1 : 0) | (x.keep ? 2 : 0);
                 __syncthreads(); /* the results are in */
             }
-#endif
-            int32_t last = 0;
-            for (;;) {
-                int32_t spins = 0;
-                while (m->req == last && !*quit && ++spins < (1 << 26)) __builtin_amdgcn_s_sleep(1);
-                if (m->req == last) return; /* done (or a replaying wave gone quiet: stop waiting) */
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                last = m->req;
-                WinRow x = win_block(W::N, m->n, m->refSeq, m->client, m->minSeq, m->local != 0);
-                int32_t l = w.lane();
-                m->s[l] = x.s, m->lc[l] = x.lc, m->lx[l] = x.lx, m->len[l] = x.rv.len, m->rseq[l] = x.rv.rseq;
-                m->v[l] = x.v, m->cp[l] = x.cp, m->st[l] = (x.settle ? 1 : 0) | (x.keep ? 2 : 0);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (l == 0) m->done = last;
-            }
         }
-#else
-        (void)quit;
 #endif
     }
+    /* Evaluate the window set under (refSeq, client): rows the MSN has passed settle into the
+     * STABLE summaries (or DEAD), entries of freed rows drop out, and every remaining row's chunk
+     * position, leaf index and perspective length go to the scratch, its length scattered onto
+     * cdel[chunk position]. Returns the sum of those lengths.
+     * One block of W::N entries at a time, in entry order: win_block, then the block's rows settled and its kept
+     * entries compacted. Every read of a block precedes its writes, and the compaction only writes positions at or
+     * before the entries read. In the tiled replay kernel (wm set) a set of more than W::N entries has its second
+     * block evaluated by the helper wave while this wave evaluates the first: the request is posted before the first
+     * barrier, the results are read from the mailbox after the second (win_helper has the matching pair). */
     MT_HD int32_t win_pass(int32_t refSeq, int32_t client) {
         MT_PROF_SCOPE(PH_WIN);
         auto& t = z.tl;
-#if MT_WIN_HELPER && defined(__HIPCC__)
-        if constexpr (TILED && W::N == 64) {
-            if (wm) return win_pass2(refSeq, client);
-        }
-#endif
-        /* NB passes of the wave at a time, stage by stage: every entry's loads of one stage are issued
-         * together (one round trip per stage, not one per stage per pass); the settling and the
-         * compaction then run pass by pass, in entry order. Every read of a block precedes its writes,
-         * and the compaction only writes entries at or before the ones read. */
-        constexpr int NB = W::N >= 64 ? MT_WIN_NB : 1;
-        int32_t n = t.wN, wpos = 0, total = 0;
-        for (int32_t b0 = 0; b0 < n; b0 += NB * W::N) {
-            int32_t rd[NB], g[NB], s[NB], v[NB], cp[NB], lx[NB];
-            bool settle[NB], keep[NB];
-#pragma unroll
-            for (int q = 0; q < NB; q++) { /* the entries (LDS in the tiled kernel) */
-                int32_t i = b0 + q * W::N + w.lane();
-                bool ok = i < n;
-                rd[q] = ok ? twrid[i] : 0;
-                g[q] = ok ? twgen[i] : -1;
-                s[q] = ok ? twslot[i] : 0;
-            }
-            /* One round trip when the row is still in the slot it was last seen in: its generation, its leaf,
-             * the slot's row id and the leaf's child count check the hint, and the row itself and its leaf's
-             * rope links are read in the same pass. */
-            RowView rv[NB];
-            int32_t lc[NB];
-#pragma unroll
-            for (int q = 0; q < NB; q++) {
-                int32_t c = s[q], l = c / MAXN;
-                uint8_t gg = z.RGEN(rd[q]); /* every load of the pass unconditional: they issue together */
-                IX lr = z.RLEAF(rd[q]), cr = z.RID(c);
-                int32_t cn = nch[l];
-                bool gok = g[q] >= 0 && gg == (uint8_t)g[q];
-                bool hit = gok & (lr == (IX)l) & ((c & (MAXN - 1)) < cn) & (cr == (IX)rd[q]);
-                rv[q] = row_view(c);
-                lc[q] = t.lch[l];
-                lx[q] = t.lix[l];
-                if (!hit) s[q] = gok ? -2 : -1; /* -2: look the row up */
-            }
-#pragma unroll
-            for (int q = 0; q < NB; q++) {
-                MT_PROF_COUNT(PH_C_WROWS, __builtin_popcountll(w.ballot(b0 + q * W::N + w.lane() < n)));
-                MT_PROF_COUNT(PH_C_WMISS, __builtin_popcountll(w.ballot(s[q] == -2)));
-            }
-#pragma unroll
-            for (int q = 0; q < NB; q++) { /* the rows that moved: leaf, slot, row */
-                if (s[q] == -2) {
-                    int32_t lf = z.RLEAF(rd[q]);
-                    int32_t c = nch[lf];
-                    s[q] = -1;
-                    for (int32_t j = 0; j < MAXN; j++)
-                        if (j < c && z.RID(lf * MAXN + j) == (IX)rd[q]) s[q] = lf * MAXN + j;
-                    if (s[q] >= 0) {
-                        rv[q] = row_view(s[q]);
-                        lc[q] = t.lch[lf];
-                        lx[q] = t.lix[lf];
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NB; q++) { /* settled, or its perspective length and chunk position */
-                settle[q] = s[q] >= 0 && settled_of(rv[q]);
-                keep[q] = s[q] >= 0 && !settle[q];
-                v[q] = cp[q] = 0;
-                if (keep[q]) {
-                    v[q] = vis_of(s[q], rv[q], refSeq, client);
-                    cp[q] = tcpos[lc[q]];
-                }
-            }
-            for (int q = 0; q < NB; q++) {
-                if (b0 + q * W::N >= n) break;
-                uint64_t m = w.ballot(settle[q]);
-                while (m) { /* a few rows per op: serial, on the values this pass read (row, leaf's chunk) */
-                    int32_t l = W::ffs(m);
-                    m &= m - 1;
-                    int32_t ss = w.bcast(s[q], l);
-                    if (w.bcast(rv[q].rseq, l) == NOREM) {
-                        t.xf[ss] = XF_STABLE;
-                        int32_t dl = w.bcast(rv[q].len, l), lcl = w.bcast(lc[q], l);
-                        int32_t nv = t.lst[ss / MAXN] + dl; /* cls mirrors lst: one read */
-                        t.lst[ss / MAXN] = nv;
-                        t.cls[lcl][w.bcast(lx[q], l)] = nv;
-                        cst_add(tcpos[lcl], dl);
-                    } else {
-                        t.xf[ss] = 0;
-                    }
-                }
-                int32_t tot;
-                int32_t off = w.excl_scan(keep[q] ? 1 : 0, &tot);
-                w.sync();
-                if (keep[q]) {
-                    int32_t o = wpos + off;
-                    twrid[o] = rd[q];
-                    twgen[o] = (uint8_t)g[q];
-                    twslot[o] = s[q];
-                    wcp[o] = cp[q];
-                    wlx[o] = (uint8_t)lx[q];
-                    wvs[o] = v[q];
-                    if (v[q]) {
-                        W::atomic_add(&cdel[cp[q]], v[q]);
-                        W::atomic_add(&gdel[cp[q] >> 6], v[q]);
-                    }
-                }
-                w.sync();
-                wpos += tot;
-                total += w.sum(v[q]);
-            }
-        }
-        t.wN = wpos;
-        return total;
-    }
-#if MT_WIN_HELPER && defined(__HIPCC__)
-    /* win_pass with the helper wave: the second block's entries evaluated by the helper while this wave evaluates the
-     * first; then both blocks settled and compacted in entry order, as win_pass does, and the rest of the set (more
-     * than 2 W::N entries) here. The compaction writes only positions below the entries still to be read. */
-    MT_HD int32_t win_pass2(int32_t refSeq, int32_t client) {
-        auto& t = z.tl;
         int32_t n = t.wN, wpos = 0, total = 0;
         const bool local = is_local(client);
+        bool split = false; /* the helper evaluates the second block */
+#if defined(__HIPCC__)
         volatile WinMail* m = wm;
-        const bool split = n > W::N;
-        if (split) { /* post the request: the second block, this perspective */
-            if (w.lane() == 0) {
-                m->n = n, m->refSeq = refSeq, m->client = client, m->minSeq = h.minSeq, m->local = local ? 1 : 0;
+        if constexpr (TILED && W::N == 64) {
+            split = m && n > W::N;
+            if (split) { /* post the request: the second block, this perspective */
+                if (w.lane() == 0) {
+                    m->n = n, m->refSeq = refSeq, m->client = client, m->minSeq = h.minSeq, m->local = local ? 1 : 0;
+                }
+                __syncthreads(); /* the helper's first barrier of the request */
             }
-#if MT_WIN_HELPER == 2
-            __syncthreads(); /* the helper's first barrier of the request */
-#else
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            wmseq++;
-            if (w.lane() == 0) m->req = wmseq;
-#endif
         }
+#endif
         for (int32_t b0 = 0; b0 < n; b0 += W::N) {
             WinRow x;
-            if (b0 == W::N && split) { /* the helper's results */
-#if MT_WIN_HELPER == 2
-                __syncthreads(); /* the helper's second barrier */
-#else
-                int32_t spins = 0;
-                while (m->done != wmseq && ++spins < (1 << 26)) __builtin_amdgcn_s_sleep(1);
-                if (m->done != wmseq) { /* the helper never answered: stop here, the document latched */
-                    fail(E_ASSERT);
-                    return total;
+            bool mine = true;
+#if defined(__HIPCC__)
+            if constexpr (TILED && W::N == 64) {
+                if (split && b0 == W::N) { /* the helper's results */
+                    __syncthreads();       /* the helper's second barrier */
+                    int32_t l = w.lane(), i = b0 + l;
+                    x.rd = i < n ? twrid[i] : 0;
+                    x.g = i < n ? twgen[i] : -1;
+                    x.s = m->s[l], x.lc = m->lc[l], x.lx = m->lx[l], x.rv.len = m->len[l], x.rv.rseq = m->rseq[l];
+                    x.v = m->v[l], x.cp = m->cp[l];
+                    int32_t st = m->st[l];
+                    x.settle = (st & 1) != 0, x.keep = (st & 2) != 0;
+                    mine = false;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
-                int32_t l = w.lane(), i = b0 + l;
-                x.rd = i < n ? twrid[i] : 0;
-                x.g = i < n ? twgen[i] : -1;
-                x.s = m->s[l], x.lc = m->lc[l], x.lx = m->lx[l], x.rv.len = m->len[l], x.rv.rseq = m->rseq[l];
-                x.v = m->v[l], x.cp = m->cp[l];
-                int32_t st = m->st[l];
-                x.settle = (st & 1) != 0, x.keep = (st & 2) != 0;
-            } else {
-                x = win_block(b0, n, refSeq, client, h.minSeq, local);
             }
+#endif
+            if (mine) x = win_block(b0, n, refSeq, client, h.minSeq, local);
+            MT_PROF_COUNT(PH_C_WROWS, __builtin_popcountll(w.ballot(b0 + w.lane() < n)));
             uint64_t msk = w.ballot(x.settle);
-            while (msk) { /* serial, on the values the block read */
+            while (msk) { /* a few rows per op: serial, on the values the block read (row, leaf's chunk) */
                 int32_t l = W::ffs(msk);
                 msk &= msk - 1;
                 int32_t ss = w.bcast(x.s, l);
                 if (w.bcast(x.rv.rseq, l) == NOREM) {
                     t.xf[ss] = XF_STABLE;
                     int32_t dl = w.bcast(x.rv.len, l), lcl = w.bcast(x.lc, l);
-                    int32_t nv = t.lst[ss / MAXN] + dl;
+                    int32_t nv = t.lst[ss / MAXN] + dl; /* cls mirrors lst: one read */
                     t.lst[ss / MAXN] = nv;
                     t.cls[lcl][w.bcast(x.lx, l)] = nv;
                     cst_add(tcpos[lcl], dl);
@@ -2260,7 +2108,6 @@ struct Replica {
         t.wN = wpos;
         return total;
     }
-#endif
     /* zero the chunk deltas of the last win_pass */
     MT_HD void win_clear() {
         int32_t n = z.tl.wN;
@@ -2601,10 +2448,6 @@ struct Replica {
         if (k >= h.nleaf) return -1;
         return lo[k] * MAXN + (t0 & 4);
     }
-#ifndef MT_SCAN_NB
-#define MT_SCAN_NB 1 /* flat-profile position scans: wave blocks (256 slots each) per round trip; 2 and 3 measured
-                        * 9 % and 27 % slower on config 3 (r04n: the second block's 16 registers spill at 8 waves) */
-#endif
     /* ---- removedClientOverlap: 8 entries inline in the cold row, then chains of 8-entry blocks
      * in a per-document pool (entries are short id + 1; 0 ends a list) ------------------------ */
     MT_HD bool ovl_has(int32_t s, int32_t client) const {
@@ -2811,7 +2654,8 @@ struct Replica {
         int32_t run = 0;
         int32_t T = h.nleaf * MAXN;
         const bool loc = is_local(client);
-        constexpr int NB = W::N >= 64 ? MT_SCAN_NB : 1; /* wave blocks whose loads are issued together */
+        constexpr int NB = 1; /* wave blocks per trip: one (2 and 3 spilled); the block form stays, since the
+                                * same scan over plain scalars changes the flat kernels' register allocation */
         for (int32_t b0 = 0; b0 < T; b0 += NB * 4 * W::N) {
             int32_t s0[NB];
             QuadRows x[NB];
@@ -3624,12 +3468,6 @@ struct Replica {
         keys[zh->nkeys] = key;
         return zh->nkeys++;
     }
-#ifndef MT_PROPS_PAR
-#define MT_PROPS_PAR 1
-#endif
-#ifndef MT_ACKANN_PAR
-#define MT_ACKANN_PAR 1
-#endif
     /* add_props on the GPU: lane k holds key slot k (its key id, the row's value and pending-key count), lane j
      * the op's j-th key / value; everything is read in one pass, the fold runs on those registers in the
      * reference's order (rewrite deletions, then the op's keys in order, new key slots in first-appearance
@@ -3788,7 +3626,7 @@ struct Replica {
     }
     MT_HD void add_props(int32_t s, const mt_kv* kv, int32_t nkv, int32_t comb, int32_t seq, bool collaborating,
                          int32_t knownFl = -1) {
-        if constexpr (W::N >= 32 && MT_PROPS_PAR) {
+        if constexpr (W::N >= 32) {
             if (nkv <= W::N) {
                 add_props_par(s, kv, nkv, comb, seq, collaborating, knownFl);
                 return;
@@ -3955,9 +3793,6 @@ struct Replica {
         /* the merged text ends where b's did */
         z.flags(a) = (uint8_t)((fa & ~(uint32_t)(RF_NLK | RF_NL)) | (fb & (RF_NLK | RF_NL)));
     }
-#ifndef MT_APPEND_BATCH
-#define MT_APPEND_BATCH 1 /* scour's text appends planned on scalars during the walk, their copies made together after it */
-#endif
     /* copy jobs of scour's append walk: lane j < nj holds job j (destination, source, units in the current arena
      * half); all of them in one wave-parallel copy, a lane per unit, every load of a block before its stores (the
      * sources are texts from before the walk, the destinations fresh space above them) */
@@ -4147,14 +3982,12 @@ struct Replica {
         keep |= pairs & ~okm;
         uint64_t app = 0; /* rows appended so far */
         uint64_t m = pairs & okm;
-#if MT_APPEND_BATCH
         /* TextSegment.append's arena work planned on the run head's text offset (prevT): copy jobs (lane j: job j)
          * and the heads whose text moved (lane: the new offset), applied after the walk; the same arena decisions
          * as append_rows. A walk that needs a GC applies what it planned and goes on through append_rows. */
         int32_t jd = 0, js = 0, jn = 0, nj = 0, ntof = 0, prevT = 0;
         uint64_t moved = 0;
         bool serial = false;
-#endif
         while (m) {
             int32_t k = W::ffs(m);
             m &= m - 1;
@@ -4162,9 +3995,7 @@ struct Replica {
                 prev = k - 1;
                 prevLen = w.bcast(r.len, prev);
                 prevFl = w.bcast(fl, prev);
-#if MT_APPEND_BATCH
                 prevT = w.bcast(tofP, k);
-#endif
             }
             int32_t lk = w.bcast(r.len, k);
             int32_t fk = w.bcast(fl, k);
@@ -4177,7 +4008,6 @@ struct Replica {
                 int32_t rp = w.bcast((int32_t)r.rid, prev), rk = w.bcast((int32_t)r.rid, k);
                 if (refs_on()) refs_append(rp, rk, prevLen);
                 uint32_t xp = TILED ? (uint32_t)w.bcast((int32_t)r.xf, prev) : 0u, xk = TILED ? (uint32_t)w.bcast((int32_t)r.xf, k) : 0u;
-#if MT_APPEND_BATCH
                 if (!serial && (prevFl & RF_PERM)) {
                     append_stat(sp, lk, xp, xk); /* PermutationSegment.append: the length, written by the compaction */
                 } else if (!serial) {
@@ -4217,10 +4047,10 @@ struct Replica {
                         copy_jobs(jd, js, jn, nj);
                         nj = 0;
                     }
-                } else
-#endif
-                /* updates z.len(sp) (read by a GC inside it) and its NL bits */
-                append_rows(sp, sk, rp, rk, prevLen, lk, (uint32_t)prevFl, (uint32_t)fk, xp, xk);
+                } else {
+                    /* updates z.len(sp) (read by a GC inside it) and its NL bits */
+                    append_rows(sp, sk, rp, rk, prevLen, lk, (uint32_t)prevFl, (uint32_t)fk, xp, xk);
+                }
                 prevLen += lk;
                 prevFl = (prevFl & ~(RF_NLK | RF_NL)) | (fk & (RF_NLK | RF_NL));
                 nlen = w.writelane(prevLen, prev, nlen);
@@ -4231,10 +4061,8 @@ struct Replica {
                 keep |= 1ull << k; /* kept: the next pair, if it tests ok, starts from this row */
             }
         }
-#if MT_APPEND_BATCH
         if (nj) copy_jobs(jd, js, jn, nj);
         if ((moved >> q) & 1) d.COLD(r.rid).toff = (uint32_t)ntof;
-#endif
 #if defined(MT_PROF) && defined(__HIP_DEVICE_COMPILE__)
         uint64_t _t2 = __builtin_amdgcn_s_memtime();
         if (prof) prof[PH_S2] += _t2 - _t1;
@@ -4982,7 +4810,7 @@ struct Replica {
             MT_PROF_SCOPE(PH_FIND);
             MT_PROF_SCOPE(PH_RSCAN);
             const bool loc = is_local(client);
-            constexpr int NB = W::N >= 64 ? MT_SCAN_NB : 1; /* wave blocks whose loads are issued together */
+            constexpr int NB = 1; /* as in find_reach */
             bool done = false;
             for (int32_t b0 = 0; b0 < T && !done; b0 += NB * 4 * W::N) {
                 int32_t s0[NB];
@@ -5124,12 +4952,9 @@ struct Replica {
             int32_t last = end < total ? end : total;
             int32_t P1 = 0, P2 = 0;
             int32_t n1 = 0, n2 = 0, k1, k2;
-#if MT_FIND2
             if constexpr (W::N >= 64) {
                 tile_find2(start + 1, last, &k1, &P1, &n1, &k2, &P2, &n2);
-            } else
-#endif
-            {
+            } else {
                 k1 = tile_find(start + 1, refSeq, client, &P1, &n1);
                 k2 = tile_find(last, refSeq, client, &P2, &n2);
             }
@@ -5138,13 +4963,10 @@ struct Replica {
                 fail(E_ASSERT);
                 return;
             }
-#if MT_FIND2
             if constexpr (W::N >= 64) {
                 leaf_find2(k1, n1, P1, start + 1, k2, n2, P2, last, refSeq, client, &tf, &Pf, &sf, &vf, &tg, &Pg, &sg,
                            &vg, &fr, &fc);
-            } else
-#endif
-            {
+            } else {
                 tf = leaf_find(k1, n1, P1, start + 1, refSeq, client, &Pf, &sf, &vf);
                 tg = leaf_find(k2, n2, P2, last, refSeq, client, &Pg, &sg, &vg);
             }
@@ -5928,7 +5750,7 @@ struct Replica {
                 int32_t rd = i < mn ? d.MRID(i) : 0;
                 uint64_t msk = w.ballot(i < mn && d.MGID(i) == gid);
                 if constexpr (W::N >= 64) {
-                    if (kind == MT_OP_INSERT || kind == MT_OP_REMOVE || (MT_ACKANN_PAR && kind == MT_OP_ANNOTATE)) {
+                    if (kind == MT_OP_INSERT || kind == MT_OP_REMOVE || kind == MT_OP_ANNOTATE) {
                         /* a lane per member row; LRU entries in member order */
                         if (msk) ack_rows(kind, rd, (msk >> w.lane()) & 1, seq, kv, nkv, rewrite);
                         continue;
@@ -7142,8 +6964,6 @@ struct Replica {
             mt_op_rec op;
             __builtin_memcpy(&op, u, sizeof(op));
             cur = i;
-            if constexpr (TILED)
-                if (pfcur) *(volatile int32_t*)pfcur = (int32_t)cur; /* the prefetch helpers run ahead of it */
             apply(op, p);
             if (h.err) return;
         }

@@ -156,16 +156,9 @@ __device__ inline void doc_stamp(DocHdr& h, int end) {
 /* K1-K4 fused: the whole event stream of a document, one wave per document. LDS = true stages the
  * whole small-profile hot image in LDS; otherwise the image stays in HBM and only the skeleton and
  * the heap (Skel, 3.5 KB for the small profile) are staged. */
-/* VAR tags a build variant compiled with other flags in its own translation unit (1: compiler-chosen
- * inlining): the kernel's name must differ, since a host launch resolves the kernel by name. */
 /* DL: the delta-event build (engines created with caps.dcap > 0) */
-#ifdef MT_NUM_SGPR /* experiment: an explicit SGPR budget for the flat kernel */
-#define MT_SGPR_ATTR __attribute__((amdgpu_num_sgpr(MT_NUM_SGPR)))
-#else
-#define MT_SGPR_ATTR
-#endif
-template <class HT, bool LDS, int MINW = 1, int SKM = 1, int VAR = 0, bool DL = false, bool LOAD = true> /* SKM: 1 Skel, 2 SkelLite, 0 none */
-__global__ __launch_bounds__(WG, MINW) MT_SGPR_ATTR void k_replay(Store<HT> st, int64_t ndocs, const mt_op_rec* ops,
+template <class HT, bool LDS, int MINW = 1, int SKM = 1, bool DL = false, bool LOAD = true> /* SKM: 1 Skel, 2 SkelLite, 0 none */
+__global__ __launch_bounds__(WG, MINW) void k_replay(Store<HT> st, int64_t ndocs, const mt_op_rec* ops,
                                               const int64_t* op_off, const uint16_t* text, const int64_t* text_off,
                                               const mt_props_rec* props, const int64_t* props_off, const mt_kv* kv,
                                               const int64_t* kv_off, ReplayAux aux) {
@@ -268,109 +261,12 @@ __global__ __launch_bounds__(WG, MINW) MT_SGPR_ATTR void k_replay(Store<HT> st, 
  * the per-leaf rope links and the zamboni heap stay in HBM (~0.2 GB per 1M-op document). An LDS copy of the
  * heap (~60 entries in use at lag 64) measured slower: a heap that can be in either memory is reached through
  * flat accesses, which wait for both counters (r04j A/B: 10.75 -> 10.33M ops/s at 256 x 300k). */
-#ifndef MT_PF_HELPERS
-#define MT_PF_HELPERS 0 /* prefetch helper waves per config-4 document (0: one wave per document; 1 and 2
-                           * measured 2.4 % and 3.2 % slower at 256 x 300k, profiles/r04f_ab) */
-#endif
-/* waves besides the replaying one in a config-4 workgroup: the prefetch helpers, or the window helper (MT_WIN_HELPER,
- * mt_core.h win_helper) */
-#ifndef MT_WIN_HELPER
-#define MT_WIN_HELPER 2 /* mt_core.h */
-#endif
-#define MT_TILED_HELPERS (MT_WIN_HELPER ? 1 : MT_PF_HELPERS)
-#ifndef MT_PF_AHEAD
-#define MT_PF_AHEAD 2 /* records ahead of the replaying wave each helper looks */
-#endif
-/* The helper waves of a config-4 workgroup (k_replay_tiled). A document's events are one dependent chain, so
- * the other SIMDs of the document's CU cannot share the replay; they run ahead of it instead: for the records
- * after the one being applied, a helper resolves each position approximately from the current summaries
- * (chunk scan over the staged LDS summaries without the window deltas, then the chunk's leaf summaries) and
- * loads what the replay will read there — the chunk's leaf-summary line, the leaf's 128-byte line and its
- * neighbour's, the leaf's row ids and child count, and the first 16 bytes of its rows' cold records — and,
- * for the zamboni that follows, the leaf of the row at the heap's top. Those reads then hit the L2 / MALL when
- * the replay makes them. Helpers only read (the summaries they scan may be mid-update: an approximate answer
- * only changes what is prefetched); every index is clamped to its array; they exit when the replay is done. */
-template <class HT>
-__device__ void tiled_prefetch(Doc<HT> v, const mt_op_rec* ops, int64_t nops, const volatile int32_t* cur,
-                               const volatile int32_t* done, const int32_t* lcord, const int32_t* lcst,
-                               const int32_t* lccnt, int32_t* sink) {
-    constexpr int NCH = HT::TL::NCH, N = HT::N, S = HT::S;
-    const HT* t = v.t;
-    const auto& tl = t->tl;
-    const typename HT::Cold* cold = v.cold();
-    WaveGPU w;
-    const int32_t lane = w.lane(), helper = (int32_t)(threadIdx.x / WG) - 1;
-    uint32_t acc = 0;
-    int64_t last = -1;
-    auto touch_leaf = [&](int32_t leaf) {
-        leaf = leaf < 0 ? 0 : (leaf >= N ? N - 1 : leaf);
-        const int32_t* line = (const int32_t*)&t->lf[leaf];
-        int32_t j = lane & 7;
-        int32_t r = t->rid[leaf * 8 + j];
-        r = r < 0 ? 0 : (r >= S ? S - 1 : r);
-        uint32_t x = lane < 32 ? (uint32_t)line[lane] : (uint32_t)t->nchild[leaf];
-        const uint32_t* cr = (const uint32_t*)&cold[r];
-        x ^= lane < 8 ? cr[0] ^ cr[1] ^ cr[2] ^ cr[3] : (uint32_t)t->rleaf[r] ^ t->rgen[r];
-        acc ^= x ^ (uint32_t)r;
-    };
-    while (!*done) {
-        int64_t k = (int64_t)*cur + 1 + helper * MT_PF_AHEAD;
-        if (k <= last) k = last + 1;
-        if (k >= nops || k > (int64_t)*cur + (helper + 1) * MT_PF_AHEAD) {
-            __builtin_amdgcn_s_sleep(2);
-            continue;
-        }
-        last = k;
-        mt_op_rec op = ops[k];
-        int32_t kind = op.kind & MT_OP_KIND_MASK;
-        if (kind > MT_OP_ANNOTATE || (op.kind & (MT_OPF_LOCAL | MT_OPF_TREE))) continue;
-        int32_t nch = tl.nchunk;
-        nch = nch < 1 ? 1 : (nch > NCH ? NCH : nch);
-        for (int32_t e = 0; e < (kind == MT_OP_INSERT ? 1 : 2); e++) {
-            int32_t pos = e ? op.pos2 : op.pos1;
-            int32_t run = 0, cp = nch - 1;
-            for (int32_t b = 0; b < nch; b += WG) { /* chunk scan over the staged STABLE summaries */
-                int32_t i = b + lane;
-                int32_t x = i < nch ? lcst[i] : 0;
-                int32_t tot;
-                int32_t q = run + w.excl_scan(x, &tot);
-                uint64_t m = w.ballot(i < nch && q + x >= pos);
-                if (m) {
-                    int32_t l = WaveGPU::ffs(m);
-                    cp = b + l;
-                    run = w.bcast(q, l);
-                    break;
-                }
-                run += tot;
-            }
-            int32_t c = lcord[cp];
-            c = c < 0 ? 0 : (c >= NCH ? NCH - 1 : c);
-            int32_t cnt = lccnt[c];
-            cnt = cnt < 1 ? 1 : (cnt > 64 ? 64 : cnt);
-            int32_t x = lane < cnt ? tl.cls[c][lane] : 0; /* the chunk's leaf summaries: one line */
-            int32_t tot;
-            int32_t q = run + w.excl_scan(x, &tot);
-            uint64_t m = w.ballot(lane < cnt && q + x >= pos);
-            int32_t li = m ? WaveGPU::ffs(m) : cnt - 1;
-            int32_t leaf = tl.cleaf[c][li];
-            touch_leaf(leaf);
-            touch_leaf(tl.cleaf[c][li + 1 < cnt ? li + 1 : li]);
-        }
-        if (t->h.heapN > 0) { /* the zamboni after it: the leaf of the row at the heap's top */
-            int32_t r = t->hrid[0];
-            r = r < 0 ? 0 : (r >= S ? S - 1 : r);
-            touch_leaf(t->rleaf[r]);
-        }
-    }
-    if (acc == 0x9e3779b9u && lane == 0) *sink = (int32_t)acc; /* keeps the loads */
-}
-
 /* NARROW (the default config-4 kernel): the zamboni heap in LDS too (~60 entries in use at lag 64: every pop and
- * push an LDS pass instead of an HBM round trip), beside a window set of MT_NARROW_W entries; a document whose
+ * push an LDS pass instead of an HBM round trip), beside a window set of Replica::NARROW_W entries; a document whose
  * heap or window set would outgrow them latches E_CAPACITY and the engine replays it in the wide variant
  * (NARROW = false: the heap in HBM, the full window set) — capacity promotion (mt_replay.hip). */
 template <class HT, bool DL = false, bool NARROW = false>
-__global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(Store<HT> st, int64_t ndocs, const mt_op_rec* ops,
+__global__ __launch_bounds__(WG * 2) void k_replay_tiled(Store<HT> st, int64_t ndocs, const mt_op_rec* ops,
                                                      const int64_t* op_off, const uint16_t* text,
                                                      const int64_t* text_off, const mt_props_rec* props,
                                                      const int64_t* props_off, const mt_kv* kv, const int64_t* kv_off,
@@ -392,10 +288,7 @@ __global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(St
     __shared__ int32_t lhseq[HL]; /* NARROW: the zamboni heap */
     __shared__ typename HT::IX lhrid[HL];
     __shared__ uint8_t lhgen[HL];
-    __shared__ int32_t pfcur, pfdone, pfsink; /* the replaying wave's record, its end, the helpers' sink */
-#if MT_WIN_HELPER
     __shared__ typename R::WinMail wmail; /* the window helper's mailbox */
-#endif
 #ifdef MT_PROF
     __shared__ uint64_t sprof[PH_N];
     for (int i = threadIdx.x; i < PH_N; i += blockDim.x) sprof[i] = 0;
@@ -429,13 +322,7 @@ __global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(St
             wave_copy(lhgen, v.t->hgen, nheap);
         }
     }
-    if (threadIdx.x == 0) { /* every path: helper waves read these after the barrier */
-        pfcur = 0;
-        pfdone = fits ? 0 : 1;
-#if MT_WIN_HELPER
-        wmail.req = wmail.done = wmail.quit = 0;
-#endif
-    }
+    if (threadIdx.x == 0) wmail.quit = 0; /* every path: the helper reads it after its first barrier */
     __syncthreads();
     if (replayer && fits) doc_stamp(zhs, 0);
     Pools p;
@@ -448,7 +335,6 @@ __global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(St
     p.vkind = aux.vkind;
     p.nvk = aux.nvk;
     if (!replayer) {
-#if MT_WIN_HELPER
         if (threadIdx.x < 2 * WG) { /* the window helper: the replaying wave's LDS views of the set and the rope */
             R hr(v, WaveGPU());
             hr.tcpos = lcpos;
@@ -456,11 +342,8 @@ __global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(St
             hr.twgen = lwgen;
             hr.twslot = lwslot;
             hr.wm = &wmail;
-            hr.win_helper(&pfdone);
+            hr.win_helper();
         }
-#else
-        tiled_prefetch<HT>(v, p.ops, p.nops, &pfcur, &pfdone, lcord, lcst, lccnt, &pfsink);
-#endif
     } else if (!fits) {
         doc_stamp(v.t->h, 0);
         R r(v, WaveGPU());
@@ -490,25 +373,23 @@ __global__ __launch_bounds__(WG * (1 + MT_TILED_HELPERS)) void k_replay_tiled(St
             r.hrd = lhrid;
             r.hgn = lhgen;
         }
-        if (MT_PF_HELPERS > 0) r.pfcur = &pfcur;
-#if MT_WIN_HELPER
         r.wm = &wmail;
-#endif
         r.replay(p);
         r.commit();
         doc_stamp(zhs, 1);
-        if (threadIdx.x == 0) *(volatile int32_t*)&pfdone = 1;
 #ifdef MT_PROF
         if (prof && threadIdx.x == 0)
             for (int i = 0; i < PH_N; i++) prof[d * PH_N + i] = r.prof[i];
 #endif
     }
-#if MT_WIN_HELPER == 2
-    if (replayer) { /* the end: the helper's last barrier (win_helper) */
+    /* Barriers, reached by both waves in the same order: the one above (the staging done, quit cleared); per window
+     * pass of more than 64 entries, win_pass's two, which pair with the two of win_helper's loop; then this one, on
+     * every path of the replaying wave (the !fits one too), which pairs with the first barrier of the helper's loop,
+     * where the helper reads quit and returns; and the last one, which both reach before the write-back. */
+    if (replayer) {
         if (threadIdx.x == 0) wmail.quit = 1;
         __syncthreads();
     }
-#endif
     __syncthreads();
     if (replayer && fits) {
         wave_copy((int32_t*)&v.t->h, (const int32_t*)&zhs, (int)(sizeof(DocHdr) / 4));
@@ -736,9 +617,6 @@ __global__ __launch_bounds__(WG) void k_seg(Store<HT> st, int64_t doc, int32_t m
  * document block, so a document may be named by several queries of a launch; the tiled profile's position index
  * keeps scratch in the block (Replica: sdel, swcp, ...), so the host launches its queries of one document one
  * after the other (mt_replay.hip read_plan). */
-#ifndef MT_TEXTS_PACKED_DEFAULT
-#define MT_TEXTS_PACKED_DEFAULT true /* k_texts' copy: Replica::packed_copy or each lane its own piece */
-#endif
 struct ReadQ {
     int64_t doc;
     int32_t ref_seq, long_client, floor;
@@ -815,9 +693,6 @@ __global__ __launch_bounds__(WG) void k_segs(Store<HT> st, int64_t m, const Read
 }
 
 /* ---- batched dumps (mt_engine_dumps): no perspective, so no status; only q.doc and q.slot are read ---- */
-#ifndef MT_DUMPS_PARALLEL_DEFAULT
-#define MT_DUMPS_PARALLEL_DEFAULT true /* k_dumps' writer: Replica::dump_wave or the serial dump */
-#endif
 /* the byte size of query i's canonical dump (size[slot]): every lane sizes one row's record per pass, the wave
  * sums them (Replica::dump_wave without a buffer); what Replica::dump(nullptr, 0) returns */
 template <class HT>
@@ -847,9 +722,6 @@ __global__ __launch_bounds__(WG) void k_dumps(Store<HT> st, int64_t m, const Rea
 
 /* ---- batched summaries (mt_engine_summaries): the summary dump (mt_oplog.h) of each query's document; as the
  * batched dumps, only q.doc and q.slot are read ---- */
-#ifndef MT_SUMMARIES_PARALLEL_DEFAULT
-#define MT_SUMMARIES_PARALLEL_DEFAULT true /* k_summaries' writer: Replica::summary_wave or the serial summary */
-#endif
 /* the byte size of query i's summary dump (size[slot]): Replica::summary_wave without a buffer, the decisions of
  * the fill */
 template <class HT>
@@ -881,9 +753,6 @@ __global__ __launch_bounds__(WG) void k_summaries(Store<HT> st, int64_t m, const
  * perspective; q.a = the position (< 0: undefined), q.b = preceding (find_tiles). `key` is the label key's id and
  * `set` the call's one label as a bitmap over the host's value ids (Replica::label_in). The walks keep no scratch in
  * the document block. A refused query (the label key was annotated on a marker) has status MT_E_UNSUPPORTED. ---- */
-#ifndef MT_TILES_PARALLEL_DEFAULT
-#define MT_TILES_PARALLEL_DEFAULT true /* k_find_tiles / k_stacks: the wave forms or the serial ones */
-#endif
 static_assert(sizeof(mt_tile_ref) == 4 * MT_TILE_WORDS, "mt_tile_ref is Replica::tile_words' five words");
 /* MergeTree.findTile per query: out[slot] (rid -1: none or refused), status[slot] */
 template <class HT, bool PAR>
@@ -1081,10 +950,10 @@ struct mt_engine {
     DevBuf vkind;
     int32_t nvk = 0;
     std::vector<uint8_t> h_vkind;
-    bool texts_packed = MT_TEXTS_PACKED_DEFAULT; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
-    bool dumps_parallel = MT_DUMPS_PARALLEL_DEFAULT; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
-    bool summaries_parallel = MT_SUMMARIES_PARALLEL_DEFAULT; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
-    bool tiles_parallel = MT_TILES_PARALLEL_DEFAULT; /* k_find_tiles' / k_stacks' walk (MT_VAR_TILES_PARALLEL) */
+    bool texts_packed = true; /* k_texts' copy (MT_VAR_TEXTS_PACKED) */
+    bool dumps_parallel = true; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
+    bool summaries_parallel = true; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
+    bool tiles_parallel = true; /* k_find_tiles' / k_stacks' walk (MT_VAR_TILES_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable

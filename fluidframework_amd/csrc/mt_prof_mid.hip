@@ -2,7 +2,7 @@
 #include "mt_kernels.h"
 
 static int32_t replay_mid(mt_engine* e) {
-    if (e->fx) return launch_replay<HotMid>(e, k_replay<HotMid, false, 1, 1, 0, true>); /* delta events */
+    if (e->fx) return launch_replay<HotMid>(e, k_replay<HotMid, false, 1, 1, true>); /* delta events */
     return launch_replay<HotMid>(e, k_replay<HotMid, false>);
 }
 

@@ -7,5 +7,5 @@
 #include "mt_kernels.h"
 
 int32_t replay_small_lds(mt_engine* e) {
-    return launch_replay<HotSmall>(e, k_replay<HotSmall, true, 1, 1, 0, false, false>);
+    return launch_replay<HotSmall>(e, k_replay<HotSmall, true, 1, 1, false, false>);
 }

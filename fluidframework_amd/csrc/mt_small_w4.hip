@@ -10,5 +10,5 @@
 #include "mt_kernels.h"
 
 int32_t replay_small_w4(mt_engine* e) {
-    return launch_replay<HotSmall>(e, k_replay<HotSmall, false, 4, 1, 0, false, false>);
+    return launch_replay<HotSmall>(e, k_replay<HotSmall, false, 4, 1, false, false>);
 }
