@@ -6290,6 +6290,108 @@ struct Replica {
         return n;
     }
 
+    /* ---- reads: PermutationVector handles (matrix permutationvector.ts, handlecache.ts) ---- */
+    /* HandleCache.getHandles(start, end) (handlecache.ts:69-83) in the local view, as one segment walk (the method's
+     * own TODO) instead of one getContainingSegment per position: every visible row that intersects [start, end)
+     * gives start-handle + offset for each of its positions in the range, or HANDLE_NONE when the row is no
+     * PermutationSegment or holds no handles (toff 0: the reference's Handle.unallocated + offset, which
+     * isHandleValid refuses whatever the offset). Position for position what k_seg's mode 3 answers. Writes at most
+     * cap handles and returns how many positions of the range the document holds.
+     * WAVE: the 8-leaves-by-8-slots pass of get_text_range; the wave writes each pass's run of handles contiguously,
+     * striding over it together (a merged row of thousands of positions is the whole wave's work, not one lane's),
+     * each position finding its row by packed_copy's 6-step search over the lanes' output offsets. Every lane must
+     * call it. Else the serial row walk of get_items, lane 0 writing. The same words either way. */
+    static constexpr int32_t HANDLE_NONE = INT32_MIN;
+    MT_HD int32_t handle_start(int32_t s) const { return (z.flags(s) & RF_PERM) ? (int32_t)cold(s).toff : 0; }
+    template <bool WAVE = true>
+    MT_HD int64_t get_handles(int32_t start, int32_t end, int32_t* out, int64_t cap) {
+        const int32_t refSeq = h.currentSeq, client = h.localShort;
+        if (start < 0) start = 0; /* positions are >= 0 */
+        int64_t n = 0;
+        int32_t P = 0; /* position of the pass's first row */
+        if constexpr (WAVE && W::N >= MAXN * MAXN) {
+            int32_t k = 0;
+            bool more = kvalid(0);
+            while (more && P < end) { /* wave-uniform: the rows at or past `end` are not visited */
+                const int32_t s = pass_row(k, more);
+                const int32_t v = s >= 0 ? vis(s, refSeq, client) : 0;
+                int32_t vtot;
+                const int32_t p = P + w.excl_scan(v, &vtot);
+                const bool hit = v > 0 && start < p + v && end > p;
+                const int32_t a = hit && start > p ? start - p : 0;
+                const int32_t b = !hit ? 0 : end - p < v ? end - p : v;
+                const int32_t h0 = hit ? handle_start(s) : 0;
+                int32_t tot;
+                const int32_t eo = w.excl_scan(b - a, &tot);
+                const int64_t room = cap - n;
+                const int32_t lim = !out || room <= 0 ? 0 : tot < room ? tot : (int32_t)room;
+                for (int32_t u0 = 0; u0 < lim; u0 += W::N) { /* wave-uniform bounds: every lane shuffles */
+                    const int32_t u = u0 + w.lane();
+                    int32_t L = 0, e = w.shfl(eo, 0);
+                    for (int32_t st = W::N >> 1; st > 0; st >>= 1) {
+                        const int32_t c = w.shfl(eo, L + st);
+                        if (c <= u) L += st, e = c;
+                    }
+                    const int32_t hb = w.shfl(h0, L), ab = w.shfl(a, L);
+                    if (u < lim) out[n + u] = hb ? hb + ab + (u - e) : HANDLE_NONE;
+                }
+                n += tot;
+                P += vtot;
+            }
+            w.sync();
+            return n;
+        }
+        const bool writer = w.lane() == 0;
+        for (int32_t k = 0; kvalid(k) && P < end; k = knext(k)) {
+            const int32_t lf = leaf_at(k), c = nch[lf];
+            for (int32_t j = 0; j < c; j++) {
+                const int32_t s = lf * MAXN + j;
+                const int32_t v = vis(s, refSeq, client), p = P;
+                P += v;
+                if (v <= 0 || !(start < p + v && end > p)) continue;
+                const int32_t a = start > p ? start - p : 0, b = end - p < v ? end - p : v;
+                const int32_t h0 = handle_start(s);
+                for (int32_t u = a; u < b; u++, n++)
+                    if (out && writer && n < cap) out[n] = h0 ? h0 + u : HANDLE_NONE;
+            }
+        }
+        w.sync();
+        return n;
+    }
+    /* PermutationVector.handleToPosition(handle, localSeq) (permutationvector.ts:198-253): the first segment in
+     * walkAllSegments order whose allocated handles hold `handle` (a removed row that is still linked matches, as in
+     * the reference), at findReconnectionPostition(segment, localSeq) + handle - start. false for the reference's two
+     * asserts: localSeq past collabWindow.localSeq (199), no segment found (245). The wave tests 64 rows per pass,
+     * each lane its own; the lanes of a pass are in document order, so the first pass with a hit and its lowest
+     * lane decide (one ballot per pass), and the walk stops there. Every lane must call it and gets the result; the
+     * one-lane host build walks the rows one by one. */
+    MT_HD bool handle_hit(int32_t s, int32_t handle) const {
+        const int32_t h0 = handle_start(s);
+        return h0 != 0 && h0 <= handle && handle < h0 + z.len(s);
+    }
+    MT_HD bool handle_to_position_wave(int32_t handle, int32_t lseq, int32_t* pos) {
+        if (lseq > zh->localSeq) return false;
+        int32_t s = -1;
+        if constexpr (W::N >= MAXN * MAXN) {
+            int32_t k = 0;
+            bool more = kvalid(0);
+            while (more && s < 0) {
+                const int32_t q = pass_row(k, more);
+                const uint64_t m = w.ballot(q >= 0 && handle_hit(q, handle));
+                if (m) s = w.bcast(q, W::ffs(m));
+            }
+        } else {
+            for (int32_t k = 0; kvalid(k) && s < 0; k = knext(k)) {
+                const int32_t lf = leaf_at(k), c = nch[lf];
+                for (int32_t j = 0; j < c && s < 0; j++)
+                    if (handle_hit(lf * MAXN + j, handle)) s = lf * MAXN + j;
+            }
+        }
+        if (s < 0) return false;
+        *pos = recon_pos(s, lseq) + handle - handle_start(s);
+        return true;
+    }
+
     /* ---- reads: getContainingSegment / getPosition (mergeTree.ts:1656-1667, 1619-1636) ---- */
     /* The row holding position pos under the perspective (searchBlock descends to the first child
      * with pos < length: the first row with P <= pos < P + vis); *off = pos - P. -1 if none. */

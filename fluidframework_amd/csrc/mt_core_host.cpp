@@ -236,6 +236,27 @@ int32_t mth_get_handle(mth_store* s, int64_t doc, int32_t pos, int32_t* out) {
     });
 }
 
+/* HandleCache.getHandles(start, end) in the local view (Replica::get_handles, the serial form): *status = 0 and the
+ * count returned (at most cap written), or *status = 16 (the engine's MT_E_ARG) and 0 for a range outside
+ * 0 <= start <= end <= length */
+int64_t mth_get_handles(mth_store* s, int64_t doc, int32_t start, int32_t end, int32_t* out, int64_t cap,
+                        int32_t* status) {
+    return with_replica(s, doc, [&](auto& r) -> int64_t {
+        const bool ok = r.d.caps.pcap > 0 && 0 <= start && start <= end && end <= r.length_local();
+        *status = ok ? 0 : 16;
+        return ok ? r.get_handles(start, end, out, cap) : 0;
+    });
+}
+
+/* PermutationVector.handleToPosition(handle, localSeq) (Replica::handle_to_position_wave, one lane): 0 and *out, or 16
+ * (MT_E_ARG) where the reference asserts */
+int32_t mth_handle_to_position(mth_store* s, int64_t doc, int32_t handle, int32_t local_seq, int32_t* out) {
+    return with_replica(s, doc, [&](auto& r) -> int32_t {
+        if (r.d.caps.pcap <= 0) return 16;
+        return r.handle_to_position_wave(handle, local_seq, out) ? 0 : 16;
+    });
+}
+
 /* pending segment groups (local ops in flight) of one doc */
 int32_t mth_pending(mth_store* s, int64_t doc) {
     return with_replica(s, doc, [](auto& r) { return r.zh->gqN; });

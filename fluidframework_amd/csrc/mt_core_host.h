@@ -12,6 +12,9 @@ mth_store* mth_create_fx(int64_t ndocs, const int32_t* caps6, int32_t dcap, int3
 mth_store* mth_create_fx2(int64_t ndocs, const int32_t* caps6, int32_t dcap, int32_t rcap, int32_t pcap);
 int64_t mth_handle_table(mth_store* s, int64_t doc, int32_t* out, int64_t cap);
 int32_t mth_get_handle(mth_store* s, int64_t doc, int32_t pos, int32_t* out);
+int64_t mth_get_handles(mth_store* s, int64_t doc, int32_t start, int32_t end, int32_t* out, int64_t cap,
+                        int32_t* status);
+int32_t mth_handle_to_position(mth_store* s, int64_t doc, int32_t handle, int32_t local_seq, int32_t* out);
 int32_t mth_ref_positions(mth_store* s, int64_t doc, int32_t* out, int32_t cap);
 int32_t mth_pending(mth_store* s, int64_t doc);
 int64_t mth_deltas(mth_store* s, int64_t doc, int32_t* out, int64_t cap, uint64_t* hash);

@@ -804,6 +804,76 @@ __global__ __launch_bounds__(WG) void k_stacks(Store<HT> st, int64_t m, const Re
         (void)r.stack_context(q.a, key, set, out + o * MT_TILE_WORDS, c, &d, &hw);
 }
 
+/* ---- batched matrix reads (mt_engine_get_handles / mt_engine_handles_to_positions / mt_engine_handle_tables): the
+ * PermutationVector reads of a SharedMatrix host, in the local view only, so no perspective. The walks keep no scratch
+ * in the document block. ---- */
+/* a handle range query (q.a = start, q.b = end) is valid when 0 <= start <= end <= the local length (the assert of
+ * getMaybeHandle, permutationvector.ts:158, and ensureRange's RangeError, handlecache.ts:102): size[slot] = end - start,
+ * else 0 and status MT_E_ARG */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_handle_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int64_t* size,
+                                                    int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    const bool ok = 0 <= q.a && q.a <= q.b && q.b <= r.length_local();
+    if (threadIdx.x == 0) size[q.slot] = ok ? (int64_t)q.b - q.a : 0, status[q.slot] = ok ? MT_OK : MT_E_ARG;
+}
+/* query i's handles into out[off[slot], off[slot + 1]) (the host's prefix sum of k_handle_sizes' sizes: an invalid
+ * query's window is empty) and nowhere else. PAR: the wave writes each pass's run together (Replica::get_handles);
+ * else the serial row walk, lane 0 writing: the same words either way. */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_handles(Store<HT> st, int64_t m, const ReadQ* qs, const int64_t* off,
+                                               int32_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    (void)r.template get_handles<PAR>(q.a, q.b, out + o, cap);
+}
+/* PermutationVector.handleToPosition per query (q.a = handle, q.b = localSeq, MT_LOCAL_SEQ_CURRENT: the replica's
+ * own): out[slot] = the position, or -1 and status MT_E_ARG where the reference asserts. PAR: 64 rows per pass
+ * (Replica::handle_to_position_wave); else k_seg's mode 6, a leaf per pass. */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_handle_positions(Store<HT> st, int64_t m, const ReadQ* qs, int32_t* out,
+                                                        int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    Replica<WaveGPU, HT> r(st.doc(q.doc), WaveGPU());
+    const int32_t lseq = q.b == MT_LOCAL_SEQ_CURRENT ? r.zh->localSeq : q.b;
+    int32_t pos = -1;
+    bool found;
+    if constexpr (PAR) {
+        found = r.handle_to_position_wave(q.a, lseq, &pos);
+    } else {
+        int32_t res[MT_SEGQ_N];
+        seg_eval<HT>(r, 6, q.a, lseq, 0, -1, 0, res);
+        found = res[0] == 1;
+        pos = res[1];
+    }
+    if (threadIdx.x == 0) out[q.slot] = found ? pos : -1, status[q.slot] = found ? MT_OK : MT_E_ARG;
+}
+/* HandleTable.snapshot() per query: size[slot] = the length of the document's `handles` array (DState.hlen) */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_handle_table_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int64_t* size) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    if (threadIdx.x == 0) size[q.slot] = st.doc(q.doc).dstate()->hlen;
+}
+/* the table's words into out[off[slot], off[slot + 1]) and nowhere else, copied by the wave */
+template <class HT>
+__global__ __launch_bounds__(WG) void k_handle_tables(Store<HT> st, int64_t m, const ReadQ* qs, const int64_t* off,
+                                                     int32_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    const Doc<HT> v = st.doc(q.doc);
+    const int64_t n = v.dstate()->hlen;
+    const int32_t* t = v.ht();
+    for (int64_t i = threadIdx.x; i < n && i < cap; i += WG) out[o + i] = t[i];
+}
+
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
  * out[2i+1] = its generation; *n = the segment count (writes at most cap pairs) */
 template <class HT>
@@ -954,6 +1024,7 @@ struct mt_engine {
     bool dumps_parallel = true; /* k_dumps' writer (MT_VAR_DUMPS_PARALLEL) */
     bool summaries_parallel = true; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
     bool tiles_parallel = true; /* k_find_tiles' / k_stacks' walk (MT_VAR_TILES_PARALLEL) */
+    bool handles_parallel = true; /* k_handles' / k_handle_positions' walk (MT_VAR_HANDLES_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
@@ -1024,6 +1095,15 @@ struct ProfOps {
                            int32_t* dcount, int64_t* dhigh, int32_t* dstatus);
     int32_t (*stacks)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t key, const uint32_t* dset,
                       const int64_t* doff, int32_t* dout, bool par);
+    /* the matrix reads */
+    int32_t (*handle_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize, int32_t* dstatus);
+    int32_t (*handles)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff, int32_t* dout,
+                       bool par);
+    int32_t (*handle_positions)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t* dout,
+                                int32_t* dstatus, bool par);
+    int32_t (*handle_table_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize);
+    int32_t (*handle_tables)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff,
+                             int32_t* dout);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1189,9 +1269,43 @@ struct Launch {
                                doff, dout);
         return launch_check(e, "k_stacks");
     }
+    static int32_t handle_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize,
+                                int32_t* dstatus) {
+        hipLaunchKernelGGL((k_handle_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dsize, dstatus);
+        return launch_check(e, "k_handle_sizes");
+    }
+    static int32_t handles(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff, int32_t* dout,
+                           bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_handles<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
+        else
+            hipLaunchKernelGGL((k_handles<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff,
+                               dout);
+        return launch_check(e, "k_handles");
+    }
+    static int32_t handle_positions(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t* dout,
+                                    int32_t* dstatus, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_handle_positions<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq,
+                               dout, dstatus);
+        else
+            hipLaunchKernelGGL((k_handle_positions<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq,
+                               dout, dstatus);
+        return launch_check(e, "k_handle_positions");
+    }
+    static int32_t handle_table_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize) {
+        hipLaunchKernelGGL((k_handle_table_sizes<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dsize);
+        return launch_check(e, "k_handle_table_sizes");
+    }
+    static int32_t handle_tables(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff,
+                                 int32_t* dout) {
+        hipLaunchKernelGGL((k_handle_tables<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
+        return launch_check(e, "k_handle_tables");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
         return ProfOps{init,   start_collab, replay, hdr,     digest,     dump,  length, text,       seg,
                        refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps,
-                       summary_sizes, summaries, find_tiles, stack_sizes, stacks};
+                       summary_sizes, summaries, find_tiles, stack_sizes, stacks,
+                       handle_sizes, handles, handle_positions, handle_table_sizes, handle_tables};
     }
 };

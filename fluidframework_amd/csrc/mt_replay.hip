@@ -878,6 +878,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value != 0 && value != 1) return MT_E_ARG;
         e->tiles_parallel = value == 1;
         return MT_OK;
+    case MT_VAR_HANDLES_PARALLEL:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->handles_parallel = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1263,12 +1267,13 @@ int64_t mt_engine_get_texts(mt_engine* e, int64_t m, const int64_t* docs, const 
 }
 
 extern "C++" {
-/* The sizing contract of the batched dumps and summaries, in one place: plan the queries, size(engine, stream, queries,
- * count, sizes) per run, the prefix sum on the host into off_out[0..m], then (when `out` is given and the total fits
- * cap: all or nothing) fill(engine, stream, queries, count, offsets, bytes) per run and one copy back. */
+/* The sizing contract of the batched dumps, summaries and handle tables, in one place: plan the queries, size(engine,
+ * stream, queries, count, sizes) per run, the prefix sum on the host into off_out[0..m], then (when `out` is given and
+ * the total fits cap: all or nothing) fill(engine, stream, queries, count, offsets, bytes) per run and one copy back.
+ * Sizes, offsets and cap count elements of `unit` bytes. */
 template <class FS, class FF>
 static int64_t windows_read(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, uint8_t* out, int64_t cap,
-                            FS&& size, FF&& fill) {
+                            FS&& size, FF&& fill, size_t unit = 1) {
     if (!e || m < 0 || cap < 0) return -MT_E_ARG;
     if (m == 0) return 0;
     if (!off_out) return -MT_E_ARG;
@@ -1296,7 +1301,7 @@ static int64_t windows_read(mt_engine* e, int64_t m, const int64_t* docs, int64_
     for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
     const int64_t total = off_out[m];
     if (!out || total > cap) return total; /* all or nothing */
-    if (ensure(e, e->tmp, (size_t)total)) return -MT_E_NOMEM;
+    if (ensure(e, e->tmp, unit * (size_t)total)) return -MT_E_NOMEM;
     uint8_t* dout = (uint8_t*)e->tmp.p;
     if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
         return -MT_E_HIP;
@@ -1304,7 +1309,8 @@ static int64_t windows_read(mt_engine* e, int64_t m, const int64_t* docs, int64_
         return fill(x, s, n, q, doff, dout);
     });
     if (rc) return -rc;
-    if (hipMemcpyAsync(out, dout, (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipMemcpyAsync(out, dout, unit * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
+        return -MT_E_HIP;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
     return total;
 }
@@ -1421,6 +1427,93 @@ int64_t mt_engine_stack_contexts(mt_engine* e, int64_t m, const int64_t* docs, c
     if (hipMemcpyAsync(out, dout, eb * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
     return total;
+}
+
+/* ---- batched matrix reads (mt_kernels.h k_handle_sizes / k_handles / k_handle_positions / k_handle_tables) ---- */
+int64_t mt_engine_get_handles(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* starts, const int32_t* ends,
+                              int64_t* off_out, int32_t* status_out, int32_t* out, int64_t cap) {
+    if (!e || e->pcap <= 0 || m < 0 || cap < 0) return -MT_E_ARG;
+    if (m == 0) return 0;
+    if (!off_out || !status_out || !starts || !ends) return -MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, starts, ends, 0, nullptr, nullptr, p);
+    if (rc) return -rc;
+    if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
+    /* the queries, their sizes, the offsets, the statuses */
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), sb = up16(8 * (size_t)m), ob = up16(8 * ((size_t)m + 1));
+    if ((rc = ensure(e, e->rq, qb + sb + ob + 4 * (size_t)m))) return -rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    int64_t* dsize = (int64_t*)(base + qb);
+    int64_t* doff = (int64_t*)(base + qb + sb);
+    int32_t* dst = (int32_t*)(base + qb + sb + ob);
+    if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->handle_sizes(x, s, n, q, dsize, dst);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(off_out + 1, dsize, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    off_out[0] = 0;
+    for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
+    const int64_t total = off_out[m];
+    if (!out || total > cap || total == 0) return total; /* all or nothing */
+    if (ensure(e, e->tmp, 4 * (size_t)total)) return -MT_E_NOMEM;
+    int32_t* dout = (int32_t*)e->tmp.p;
+    if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    const bool par = e->handles_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->handles(x, s, n, q, doff, dout, par);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(out, dout, 4 * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    return total;
+}
+
+int32_t mt_engine_handles_to_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* handles,
+                                       const int32_t* local_seqs, int32_t* out, int32_t* status_out) {
+    if (!e || e->pcap <= 0 || m < 0) return MT_E_ARG;
+    if (m == 0) return MT_OK;
+    if (!handles || !out || !status_out) return MT_E_ARG;
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, handles, local_seqs, MT_LOCAL_SEQ_CURRENT, nullptr, nullptr, p);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), rb = up16(4 * (size_t)m);
+    if ((rc = ensure(e, e->rq, qb + 2 * rb))) return rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    int32_t* dres = (int32_t*)(base + qb);
+    int32_t* dst = (int32_t*)(base + qb + rb);
+    HIPCHK(e, hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    const bool par = e->handles_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->handle_positions(x, s, n, q, dres, dst, par);
+    });
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(out, dres, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return MT_OK;
+}
+
+int64_t mt_engine_handle_tables(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, int32_t* out,
+                                int64_t cap) {
+    if (!e || e->pcap <= 0) return -MT_E_ARG;
+    return windows_read(
+        e, m, docs, off_out, (uint8_t*)out, cap,
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, int64_t* dsize) {
+            return x->ops->handle_table_sizes(x, s, n, q, dsize);
+        },
+        [&](mt_engine* x, hipStream_t s, int64_t n, const ReadQ* q, const int64_t* doff, uint8_t* dout) {
+            return x->ops->handle_tables(x, s, n, q, doff, (int32_t*)dout);
+        },
+        4);
 }
 
 /* k_segs over m queries: res[i * MT_SEGQ_N ..] = query i's words; status_out[i] = MT_E_UNSUPPORTED for a refused one */

@@ -45,6 +45,7 @@ MT_VAR_SMALL_WAVES, MT_VAR_TILED_WIDE, MT_VAR_CHUNK_DOCS, MT_VAR_TEXTS_PACKED = 
 MT_VAR_DUMPS_PARALLEL = 5
 MT_VAR_SUMMARIES_PARALLEL = 6
 MT_VAR_TILES_PARALLEL = 7
+MT_VAR_HANDLES_PARALLEL = 8
 
 
 def lib() -> ctypes.CDLL:
@@ -122,6 +123,11 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_get_containing_segments.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_resolve_remote_client_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
         L.mt_engine_adjust_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+        L.mt_engine_get_handles.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64]
+        L.mt_engine_get_handles.restype = i64
+        L.mt_engine_handles_to_positions.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+        L.mt_engine_handle_tables.argtypes = [vp, i64, vp, vp, vp, i64]
+        L.mt_engine_handle_tables.restype = i64
         L.mt_engine_ndocs.argtypes = [vp]
         L.mt_engine_ndocs.restype = i64
         _LIB = L
@@ -530,6 +536,77 @@ class Engine:
         status)."""
         return self._positions(self.L.mt_engine_adjust_positions, "adjust_positions", pos, docs, from_seqs,
                                long_clients)
+
+    # ---- batched matrix reads (mt_engine_get_handles / _handles_to_positions / _handle_tables): the local view ----
+    def get_handles(self, starts, ends, docs=None):
+        """HandleCache.getHandles(start, end) per query (mt_engine_get_handles): (off, status, handles); query i's
+        handles of local positions [starts[i], ends[i]) are handles[off[i]:off[i+1]], each what get_handle returns for
+        its position (INT32_MIN = unallocated). status[i] is 0, or MT_E_ARG for a range outside 0 <= start <= end <=
+        length (its window is empty). A scalar start / end is broadcast. One call: the buffer is sized by the ranges' widths."""
+        m, d, _, _ = self._queries(docs, None, None)
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(starts, np.int32), (m,)))
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(ends, np.int32), (m,)))
+        off, st = np.zeros(m + 1, np.int64), np.zeros(m, np.int32)
+        if not m:
+            return off, st, np.zeros(0, np.int32)
+
+        def call(out, cap):
+            n = self.L.mt_engine_get_handles(self.h, m, self._pn(d), _p(a), _p(b), _p(off), _p(st), out, cap)
+            if n < 0:
+                raise EngineError(f"get_handles failed {n}", -n)
+            return n
+        # a valid window is end - start long, so the ranges' widths bound the total: one call fills (the C call sizes
+        # and fills in one trip when the total fits cap); only an absurd bound takes a size query first
+        bound = int(np.maximum(b.astype(np.int64) - a, 0)[a >= 0].sum())
+        if bound <= 1 << 26:
+            buf = np.zeros(max(bound, 1), np.int32)
+            n = call(_p(buf), bound)
+        else:
+            n = call(None, 0)
+            buf = np.zeros(max(n, 1), np.int32)
+            if n and call(_p(buf), n) != n:
+                raise EngineError("get_handles size changed")
+        return off, st, buf[:n]
+
+    def handles_to_positions(self, handles, local_seqs=None, docs=None):
+        """PermutationVector.handleToPosition(handle, localSeq) per query (mt_engine_handles_to_positions):
+        (positions, status); status[i] is 0, or MT_E_ARG where the reference asserts (its position is then -1).
+        local_seqs None = each replica's current localSeq."""
+        m, d, _, _ = self._queries(docs, None, None)
+        hd = np.ascontiguousarray(np.broadcast_to(np.asarray(handles, np.int32), (m,)))
+        ls = None if local_seqs is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(local_seqs, np.int32), (m,)))
+        out, st = np.full(m, -1, np.int32), np.zeros(m, np.int32)
+        if m:
+            self._check(self.L.mt_engine_handles_to_positions(self.h, m, self._pn(d), _p(hd), self._pn(ls), _p(out),
+                                                              _p(st)), "handles_to_positions")
+        return out, st
+
+    def handle_tables(self, docs=None):
+        """HandleTable.snapshot() of every query's document (mt_engine_handle_tables): (off, tables); query i's table
+        is tables[off[i]:off[i+1]], what handle_table(docs[i]) returns. A size query and a fill the first time, then one call
+        while the total fits the largest seen."""
+        m, d, _, _ = self._queries(docs, None, None)
+        off = np.zeros(m + 1, np.int64)
+        if not m:
+            return off, np.zeros(0, np.int32)
+
+        def call(out, cap):
+            n = self.L.mt_engine_handle_tables(self.h, m, self._pn(d), _p(off), out, cap)
+            if n < 0:
+                raise EngineError(f"handle_tables failed {n}", -n)
+            return n
+        # the total is not known from the arguments: the first call on an engine sizes and then fills; later calls try
+        # a buffer of the largest total seen first, which the C call fills in one trip when the total still fits
+        cap = getattr(self, "_tables_cap", 0)
+        buf = np.zeros(max(cap, 1), np.int32)
+        n = call(_p(buf), cap) if cap else call(None, 0)
+        if n > cap:
+            buf = np.zeros(n, np.int32)
+            if call(_p(buf), n) != n:
+                raise EngineError("handle_tables size changed")
+        self._tables_cap = max(cap, n)
+        return off, buf[:n]
 
     def get_items(self, doc: int, start: int, end: Optional[int] = None) -> list:
         """SharedSequence.getItems(start, end) (sequence sharedSequence.ts:150-183) of a SubSequence document in the

@@ -133,6 +133,17 @@ export declare class ReplayEngine {
     findTiles(queries: { doc: number; pos?: number; preceding?: boolean }[], label: string): (TileRef | { unsupported: true } | undefined)[];
     /** Client.getStackContext(pos, [label])[label] for many replicas (mt_engine_stack_contexts): bottom first */
     stackContexts(queries: { doc: number; pos?: number }[], label: string): (TileRef[] | { unsupported: true })[];
+    /** HandleCache.getHandles(start, end) (handlecache.ts:69-83, behind PermutationVector.getMaybeHandle) for many
+     *  replicas in one launch (mt_engine_get_handles; engines with caps.pcap > 0): the handles of local positions
+     *  [start, end), -2^31 (Handle.unallocated) for a position without one; undefined for a range outside
+     *  0 <= start <= end <= length, where the reference asserts */
+    getHandles(queries: { doc: number; start: number; end: number }[]): (Int32Array | undefined)[];
+    /** PermutationVector.handleToPosition(handle, localSeq) (permutationvector.ts:198-253) for many replicas in one
+     *  launch (mt_engine_handles_to_positions); localSeq defaults to the replica's current one; undefined where the
+     *  reference asserts */
+    handlesToPositions(queries: { doc: number; handle: number; localSeq?: number }[]): (number | undefined)[];
+    /** HandleTable.snapshot() of every listed document (default: all) in one call (mt_engine_handle_tables) */
+    handleTables(docs?: number[]): Int32Array[];
     longIndex(name: string): number;
 }
 
@@ -182,6 +193,8 @@ export declare class GpuClient {
     getAllocatedHandle(pos: number): number;
     /** PermutationVector.getMaybeHandle: -2^31 (Handle.unallocated) when the row has none */
     getMaybeHandle(pos: number): number;
+    /** the handles of positions [start, end) in one walk (ReplayEngine.getHandles); throws outside the vector */
+    getHandles(start: number, end: number): Int32Array;
     /** HandleTable.snapshot() of this replica's PermutationVector */
     handleTable(): Int32Array;
     getLength(): number;

@@ -36,6 +36,7 @@ const RANGE_LABELS_KEY = "referenceRangeLabels"; // reservedRangeLabelsKey (merg
 const LABEL_SET_WORDS = 1024, TILE_WORDS = 5; // MT_LABEL_SET_WORDS, MT_TILE_WORDS (include/mt_engine.h)
 const E_UNSUPPORTED = 4; // MT_E_UNSUPPORTED
 const HANDLE_UNALLOCATED = -0x80000000; // Handle.unallocated (matrix handletable.ts:11)
+const LOCAL_SEQ_CURRENT = -0x80000000; // MT_LOCAL_SEQ_CURRENT (include/mt_engine.h): the replica's own localSeq
 const SEG = { TEXT: 0, MARKER: 1, PERM: 2, RUN: 3 }; // RUN: SubSequence items (mt_oplog.h MT_SEG_RUN)
 const SEG_RELPOS = 0x80; // positions relative to markers (mt_oplog.h MT_SEG_RELPOS)
 const MARKER_ID_KEY = "markerId"; // reservedMarkerIdKey
@@ -461,6 +462,41 @@ class ReplayEngine {
         return queries.map((_, i) => (r.status[i] === E_UNSUPPORTED ? { unsupported: true }
             : Array.from({ length: r.counts[i] }, (_x, k) => tileOf(r.entries, r.offsets[i] + k))));
     }
+
+    /* The PermutationVector reads of a SharedMatrix host for many replicas per launch (engines created with caps.pcap >
+     * 0), in each replica's local view. getHandles (mt_engine_get_handles; HandleCache.getHandles, handlecache.ts:69-83,
+     * the window behind getMaybeHandle): queries is an array of {doc, start, end}; the answer per query is the Int32Array
+     * of the handles of positions [start, end), each what GpuClient.getMaybeHandle returns for its position (-2^31 =
+     * Handle.unallocated), or undefined for a range outside 0 <= start <= end <= length, where the reference asserts. */
+    getHandles(queries) {
+        this.flush();
+        const docs = queries.map((q) => q.doc);
+        checkDocs(this, docs);
+        const r = addon.getHandles(this.h, docs, Int32Array.from(queries, (q) => q.start), Int32Array.from(queries, (q) => q.end));
+        return queries.map((_, i) => (r.status[i] !== 0 ? undefined : r.handles.subarray(r.offsets[i], r.offsets[i + 1])));
+    }
+
+    /* PermutationVector.handleToPosition(handle, localSeq) per query (mt_engine_handles_to_positions;
+     * permutationvector.ts:198-253): queries is an array of {doc, handle, localSeq (default: the replica's current one)};
+     * the answer per query is the position, or undefined where the reference asserts (no segment holds the handle, or
+     * localSeq is past the replica's) */
+    handlesToPositions(queries) {
+        this.flush();
+        const docs = queries.map((q) => q.doc);
+        checkDocs(this, docs);
+        const ls = Int32Array.from(queries, (q) => (q.localSeq === undefined || q.localSeq === null ? LOCAL_SEQ_CURRENT : q.localSeq));
+        const [pos, st] = addon.handlesToPositions(this.h, docs, Int32Array.from(queries, (q) => q.handle), ls);
+        return queries.map((_, i) => (st[i] !== 0 ? undefined : pos[i]));
+    }
+
+    /* HandleTable.snapshot() of every listed document (all by default) as Int32Arrays over one allocation
+     * (mt_engine_handle_tables), each what GpuClient.handleTable returns */
+    handleTables(docs) {
+        this.flush();
+        checkDocs(this, docs);
+        const { tables, offsets } = addon.handleTables(this.h, docs);
+        return Array.from({ length: offsets.length - 1 }, (_, i) => tables.subarray(offsets[i], offsets[i + 1]));
+    }
 }
 
 /* entry i of a marker-query result (MT_TILE_WORDS words: rid, gen, ordinal, position, refType) */
@@ -662,6 +698,14 @@ class GpuClient {
     }
 
     getMaybeHandle(pos) { return addon.getHandle(this.read(), this.doc, pos); }
+
+    /* the handles of positions [start, end) in one walk (ReplayEngine.getHandles for this replica); throws where
+     * getMaybeHandle would for a position of the range */
+    getHandles(start, end) {
+        const [r] = this.engine.getHandles([{ doc: this.doc, start, end }]);
+        if (r === undefined) throw new RangeError(`getHandles: [${start}, ${end}) is outside the vector`);
+        return r;
+    }
 
     handleTable() { return addon.handleTable(this.read(), this.doc); }
 

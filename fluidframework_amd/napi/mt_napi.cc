@@ -824,6 +824,118 @@ static napi_value js_stack_contexts(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* offsets as a JS array of numbers */
+static napi_value offsets_of(napi_env env, const std::vector<int64_t>& off, size_t m) {
+    napi_value offs;
+    NAPI_OK(napi_create_array_with_length(env, m + 1, &offs));
+    for (size_t i = 0; i <= m; i++) NAPI_OK(napi_set_element(env, offs, (uint32_t)i, num(env, (double)off[i])));
+    return offs;
+}
+
+/* getHandles(h, docs, starts, ends) -> {handles: Int32Array, offsets: number[], status: Int32Array}: the handles of the
+ * local positions [starts[i], ends[i]) per query (mt_engine_get_handles; HandleCache.getHandles); docs is an array of
+ * document ids, starts and ends Int32Arrays of its length; query i's handles are handles[offsets[i] .. offsets[i+1]),
+ * INT32_MIN for an unallocated position; status[i] is MT_E_ARG for a range outside 0 <= start <= end <= length. One call
+ * where the ranges' widths bound the total (a valid window is end - start long), else a size query and a fill. */
+static napi_value js_get_handles(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = false;
+    if (!e || !docs_of(env, argv[1], &docs, &all)) return nullptr;
+    void *pa, *pb;
+    size_t la, lb;
+    if (!view_of(env, argv[2], &pa, &la, napi_int32_array) || !view_of(env, argv[3], &pb, &lb, napi_int32_array))
+        return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (la != m || lb != m) return throw_status(env, e, MT_E_ARG, "getHandles (array lengths)");
+    const int64_t* dp = all ? nullptr : docs.data();
+    const int32_t *a = (const int32_t*)pa, *b = (const int32_t*)pb;
+    std::vector<int64_t> off(m + 1, 0);
+    std::vector<int32_t> st(m + 1, 0);
+    int64_t bound = 0;
+    for (size_t i = 0; i < m; i++)
+        if (a[i] >= 0 && b[i] > a[i]) bound += (int64_t)b[i] - a[i];
+    const bool guess = bound <= ((int64_t)1 << 26);
+    std::vector<int32_t> buf((size_t)(guess ? bound : 0) + 1);
+    int64_t n = mt_engine_get_handles(e, (int64_t)m, dp, a, b, off.data(), st.data(), guess ? buf.data() : nullptr,
+                                      guess ? bound : 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_get_handles (engine created without caps.pcap?)");
+    if (!guess && n > 0) {
+        buf.resize((size_t)n + 1);
+        int64_t n2 = mt_engine_get_handles(e, (int64_t)m, dp, a, b, off.data(), st.data(), buf.data(), n);
+        if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_get_handles");
+    }
+    napi_value out, offs = offsets_of(env, off, m), h = i32_array(env, buf.data(), (size_t)n), s = i32_array(env, st.data(), m);
+    if (!offs || !h || !s) return nullptr;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "handles", h));
+    NAPI_OK(napi_set_named_property(env, out, "offsets", offs));
+    NAPI_OK(napi_set_named_property(env, out, "status", s));
+    return out;
+}
+
+/* handlesToPositions(h, docs, handles, localSeqs) -> [Int32Array positions (-1 where the reference asserts), Int32Array
+ * status]: PermutationVector.handleToPosition per query (mt_engine_handles_to_positions); handles and localSeqs are
+ * Int32Arrays of docs' length, a localSeqs entry MT_LOCAL_SEQ_CURRENT (INT32_MIN) = the replica's current localSeq */
+static napi_value js_handles_to_positions(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = false;
+    if (!e || !docs_of(env, argv[1], &docs, &all)) return nullptr;
+    void *ph, *pl;
+    size_t lh, ll;
+    if (!view_of(env, argv[2], &ph, &lh, napi_int32_array) || !view_of(env, argv[3], &pl, &ll, napi_int32_array))
+        return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (lh != m || ll != m) return throw_status(env, e, MT_E_ARG, "handlesToPositions (array lengths)");
+    std::vector<int32_t> out(m + 1, -1), st(m + 1, 0);
+    int32_t rc = mt_engine_handles_to_positions(e, (int64_t)m, all ? nullptr : docs.data(), (const int32_t*)ph,
+                                                (const int32_t*)pl, out.data(), st.data());
+    if (rc) return throw_status(env, e, rc, "mt_engine_handles_to_positions (engine created without caps.pcap?)");
+    napi_value res, a = i32_array(env, out.data(), m), b = i32_array(env, st.data(), m);
+    if (!a || !b) return nullptr;
+    NAPI_OK(napi_create_array_with_length(env, 2, &res));
+    NAPI_OK(napi_set_element(env, res, 0, a));
+    NAPI_OK(napi_set_element(env, res, 1, b));
+    return res;
+}
+
+/* handleTables(h, docs?) -> {tables: Int32Array, offsets: number[]}: HandleTable.snapshot() of every named document
+ * (mt_engine_handle_tables; docs omitted: every document); document i's table is tables[offsets[i] .. offsets[i+1]) */
+static napi_value js_handle_tables(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 1) {
+        napi_throw_type_error(env, nullptr, "missing arguments");
+        return nullptr;
+    }
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs;
+    bool all = true;
+    if (!e || (argc > 1 && !docs_of(env, argv[1], &docs, &all))) return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    const int64_t* dp = all ? nullptr : docs.data();
+    std::vector<int64_t> off(m + 1, 0);
+    int64_t n = mt_engine_handle_tables(e, (int64_t)m, dp, off.data(), nullptr, 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_handle_tables (engine created without caps.pcap?)");
+    std::vector<int32_t> buf((size_t)n + 1);
+    if (n > 0) {
+        int64_t n2 = mt_engine_handle_tables(e, (int64_t)m, dp, off.data(), buf.data(), n);
+        if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_handle_tables");
+    }
+    napi_value out, offs = offsets_of(env, off, m), t = i32_array(env, buf.data(), (size_t)n);
+    if (!offs || !t) return nullptr;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "tables", t));
+    NAPI_OK(napi_set_named_property(env, out, "offsets", offs));
+    return out;
+}
+
 /* handleToPosition(h, doc, handle, localSeq) -> number */
 static napi_value js_handle_to_position(napi_env env, napi_callback_info info) {
     napi_value argv[4];
@@ -920,7 +1032,9 @@ static napi_value init(napi_env env, napi_value exports) {
                {"submitDocs", js_submit_docs}, {"docError", js_doc_error}, {"setValueKinds", js_set_value_kinds},
                {"getLengths", js_get_lengths}, {"getTexts", js_get_texts}, {"adjustPositions", js_adjust_positions},
                {"dumps", js_dumps},         {"summaries", js_summaries},
-               {"findTiles", js_find_tiles}, {"stackContexts", js_stack_contexts}};
+               {"findTiles", js_find_tiles}, {"stackContexts", js_stack_contexts},
+               {"getHandles", js_get_handles}, {"handlesToPositions", js_handles_to_positions},
+               {"handleTables", js_handle_tables}};
     for (auto& f : fns) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.cb, nullptr, &fn));

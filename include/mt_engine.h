@@ -146,9 +146,14 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *   MT_VAR_TILES_PARALLEL (0 | 1): how mt_engine_find_tiles and mt_engine_stack_contexts walk: 1 = the wave classifies a
  *     pass of 64 rows at once, 0 = the serial walk of the host core (a second device check, and the A/B baseline);
  *     takes effect at the next such call.
+ *   MT_VAR_HANDLES_PARALLEL (0 | 1): how mt_engine_get_handles and mt_engine_handles_to_positions walk: 1 = the wave
+ *     takes a pass of 64 rows at once (and writes a pass's handles together), 0 = the serial walk of the host core and
+ *     the single call's leaf-per-pass search (a second device check, and the A/B baseline); takes effect at the next
+ *     such call.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
 enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4,
-       MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6, MT_VAR_TILES_PARALLEL = 7 };
+       MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6, MT_VAR_TILES_PARALLEL = 7,
+       MT_VAR_HANDLES_PARALLEL = 8 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -356,6 +361,38 @@ int64_t mt_engine_handle_table(mt_engine* e, int64_t doc, int32_t* out, int64_t 
 /* PermutationVector.getMaybeHandle(pos) (permutationvector.ts:157-161, HandleCache.getHandle): the handle of
  * local position pos (segment start + offset; INT32_MIN = Handle.unallocated when the segment has none). */
 int32_t mt_engine_get_handle(mt_engine* e, int64_t doc, int32_t pos, int32_t* out);
+/* ---- batched matrix reads (engines created with caps.pcap > 0, else MT_E_ARG): the PermutationVector reads a
+ * SharedMatrix host makes between replays, m queries in one call, one wave each, in the local view (no perspective).
+ * The call contract is that of mt_engine_get_texts / mt_engine_find_tiles: docs == NULL = documents 0..m-1; documents
+ * may repeat, in any order; m == 0 touches nothing; promoted documents answer from their engines; the queries that
+ * name one tiled document go in successive launches; the return value is for engine-level errors only, and
+ * status_out[i] (required) is MT_OK or the code the single call returns for the query (MT_E_ARG where the reference
+ * asserts or throws), which does not fail the call. */
+/* HandleCache.getHandles(start, end) (handlecache.ts:69-83, what fills the cache PermutationVector.getMaybeHandle reads,
+ * permutationvector.ts:157-161; matrix.ts:168,179,278,280) per query: the handles of local positions [starts[i],
+ * ends[i]), one segment walk per query instead of one getContainingSegment per position. Each handle is what
+ * mt_engine_get_handle returns for its position: the segment's start + offset, and INT32_MIN for every position of a
+ * segment without handles, whatever its offset (the reference computes Handle.unallocated + offset = -2^31 + offset
+ * there, no valid handle either: isHandleValid is all that ever looks at it). A query is valid when 0 <= start <= end
+ * <= getLength(); any other (the assert of getMaybeHandle, ensureRange's RangeError) has status MT_E_ARG and an empty
+ * window. Returns the total handle count (<0: -MT_E_*) and always fills off_out[0..m]: query i's handles are
+ * out[off_out[i] .. off_out[i+1]). `out` is written only when the total fits cap: all or nothing; out == NULL is the
+ * size query. */
+int64_t mt_engine_get_handles(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* starts, const int32_t* ends,
+                              int64_t* off_out, int32_t* status_out, int32_t* out, int64_t cap);
+/* PermutationVector.handleToPosition(handle, localSeq) (permutationvector.ts:198-253; once per pending cell op on
+ * reconnect, matrix.ts:532-533) per query, as mt_engine_handle_to_position: out[i] = the position, or -1 with status
+ * MT_E_ARG where the reference asserts (permutationvector.ts:199, 245). local_seqs == NULL (or an entry
+ * MT_LOCAL_SEQ_CURRENT) = the replica's collabWindow.localSeq, the reference's default argument. */
+#define MT_LOCAL_SEQ_CURRENT INT32_MIN
+int32_t mt_engine_handles_to_positions(mt_engine* e, int64_t m, const int64_t* docs, const int32_t* handles,
+                                       const int32_t* local_seqs, int32_t* out, int32_t* status_out);
+/* HandleTable.snapshot() (handletable.ts:80-82; permutationvector.ts:265, once per vector per summary) of every query's
+ * document, as mt_engine_handle_table: off_out[0..m] in entries, query i's table is out[off_out[i] .. off_out[i+1]).
+ * No perspective and no status; the sizing contract is mt_engine_dumps' (the total returned, all or nothing, out ==
+ * NULL the size query). */
+int64_t mt_engine_handle_tables(mt_engine* e, int64_t m, const int64_t* docs, int64_t* off_out, int32_t* out,
+                                int64_t cap);
 /* caps.rcap of the engine (the row length of mt_engine_ref_positions' pos_out) */
 int32_t mt_engine_ref_capacity(const mt_engine* e);
 /* Per-doc counters: nleaf, high-water row slots, high-water heap, events applied. */

@@ -599,6 +599,66 @@ def make_tiles(node: str) -> None:
           f"{max((len(st) for st in ans['stacks']), default=0)}); {len(keep)} whole dumps", flush=True)
 
 
+def make_hvec(node: str) -> None:
+    """tests/golden/refhvec.npz: the hand-built PermutationVector read cases (tests/hvec_logs.py) replayed by the
+    reference Client with PermutationVector's handle bookkeeping (tools/ref_replay.mjs --handles), and its answers to
+    each case's queries (handlequeries.json): per handle range the raw segment.start + offset of every position or
+    "throws", per (handle, localSeq) handleToPosition's result or "throws"; every document's HandleTable.snapshot().
+    Every case's witness must hold on the reference's dump, which the fixture keeps whole. Every query has an answer or
+    a recorded throw."""
+    import hvec_logs as hl
+    cs = hl.cases()
+    b = hl.batch(cs)
+    rq, hq = hl.queries(cs)
+    d = os.path.join(SCRATCH, "hvec")
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, "handlequeries.json"), "w") as f:
+        json.dump({"ranges": [list(q) for q in rq], "positions": [list(q) for q in hq]}, f)
+    dumps, info, secs, _ = run_reference(b, d, node, interner=hl.interner(), extra=("--handles",))
+    parsed = [ol.parse_dump(x) for x in dumps]
+    for c, p in zip(cs, parsed):
+        if not c.witness(*p):
+            raise RuntimeError(f"{c.name}: the witness does not hold on the reference's dump: "
+                               f"{p[0]} {[(x['len'], x['start']) for x in p[1]][:24]}")
+    ans = json.load(open(os.path.join(d, "ref_hvec.json")))
+    assert len(ans["ranges"]) == len(rq) and len(ans["positions"]) == len(hq), "a query has no answer"
+    for q, a in zip(rq, ans["ranges"]):
+        assert ("throws" in a) != ("handles" in a) and ("throws" in a or len(a["handles"]) == q[2] - q[1]), (q, a)
+    for q, a in zip(hq, ans["positions"]):
+        assert ("throws" in a) != ("pos" in a), (q, a)
+    ht = json.load(open(os.path.join(d, "ref_handles.json")))
+    tables = [np.asarray(ht[str(i)], np.int32) for i in range(b.ndocs)]
+    flat = [x for a in ans["ranges"] for x in a.get("handles", [])]
+    np.savez_compressed(
+        os.path.join(GOLDEN, "refhvec.npz"), log_sha256=log_sha(b), names=np.asarray([c.name for c in cs]),
+        digests=np.asarray([fnv1a64(x) for x in dumps], np.uint64),
+        dumps=np.frombuffer(b"".join(dumps), np.uint8),
+        dump_off=np.concatenate([[0], np.cumsum([len(x) for x in dumps])]).astype(np.int64),
+        range_doc=np.asarray([q[0] for q in rq], np.int32), range_start=np.asarray([q[1] for q in rq], np.int32),
+        range_end=np.asarray([q[2] for q in rq], np.int32),
+        range_throws=np.asarray(["throws" in a for a in ans["ranges"]], bool),
+        # throws that are the batched call's validity rule, not reference behaviour (a reversed range, an empty range
+        # outside [0, length]: the reference's getHandles would return [] for them)
+        range_rule_throws=np.asarray([bool(a.get("rule")) for a in ans["ranges"]], bool),
+        range_off=np.concatenate([[0], np.cumsum([len(a.get("handles", [])) for a in ans["ranges"]])]).astype(np.int64),
+        range_handles=np.asarray(flat, np.int64),  # raw: Handle.unallocated + offset where the segment has no handles
+        pos_doc=np.asarray([q[0] for q in hq], np.int32), pos_handle=np.asarray([q[1] for q in hq], np.int32),
+        pos_local_seq=np.asarray([-1 if q[2] is None else q[2] for q in hq], np.int32),  # -1: the default argument
+        pos_throws=np.asarray(["throws" in a for a in ans["positions"]], bool),
+        pos_answers=np.asarray([a.get("pos", -1) for a in ans["positions"]], np.int32),
+        tables=np.concatenate(tables), table_off=np.cumsum([0] + [len(t) for t in tables]).astype(np.int64),
+        source=("packages/dds/merge-tree/src + matrix handletable.ts (reference, type-erased by tools/ts_erase.py) under "
+                "node by tools/ref_replay.mjs --handles with handlequeries.json: HandleCache.getHandles and "
+                "PermutationVector.handleToPosition restated over the reference Client after each document's replay; "
+                "a range throw marked in range_rule_throws (reversed, or empty outside [0, length]) is the batched call's "
+                "validity rule, decided here and not observed: the reference's getHandles returns [] for such a range; "
+                "logs: tests/hvec_logs.py"))
+    nt, pt = int(sum("throws" in a for a in ans["ranges"])), int(sum("throws" in a for a in ans["positions"]))
+    print(f"refhvec: {b.ndocs} docs, {b.nops} records, every witness holds; {len(rq)} handle ranges ({nt} throw, "
+          f"{len(flat)} handles), {len(hq)} handleToPosition queries ({pt} throw); tables "
+          f"{min(len(t) for t in tables)}..{max(len(t) for t in tables)} entries", flush=True)
+
+
 def make_props(node: str) -> None:
     """tests/golden/refprops.npz: the hand-built property-manager cases (tests/prop_logs.py: key slots and op widths,
     pending-key counts, rewrites, combining ops, zamboni over 24 keys, the cap cases) replayed by the reference: per
@@ -1331,6 +1391,7 @@ def main() -> None:
     ap.add_argument("--reconnect", action="store_true", help="write the hand-built reconnect fixture (refreconnect.npz) only")
     ap.add_argument("--inserts", action="store_true", help="write the insert placement / split fixture (refinserts.npz) only")
     ap.add_argument("--tiles", action="store_true", help="write the marker-query fixture (reftiles.npz) only")
+    ap.add_argument("--hvec", action="store_true", help="write the batched PermutationVector read fixture (refhvec.npz) only")
     ap.add_argument("--props", action="store_true", help="write the property-manager fixture (refprops.npz) only")
     ap.add_argument("--sessions", action="store_true", help="write the many-client fixtures (refsess_*.npz) only")
     args = ap.parse_args()
@@ -1352,6 +1413,9 @@ def main() -> None:
         return
     if args.tiles:
         make_tiles(args.node)
+        return
+    if args.hvec:
+        make_hvec(args.node)
         return
     if args.props:
         make_props(args.node)

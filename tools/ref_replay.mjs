@@ -681,6 +681,50 @@ function allSegments(client) {
     client.mergeTree.walkAllSegments(client.mergeTree.root, (seg) => { segs.push(seg); return true; });
     return segs;
 }
+// optional PermutationVector queries (--handles; handlequeries.json: {ranges: [[doc, start, end], ...], positions:
+// [[doc, handle, localSeq | null], ...]}; null = the default argument) after the doc's replay -> ref_hvec.json, restated
+// over the reference Client as getAllocatedHandle is above. An assert or error the reference raises is the answer
+// "throws", not an error of the run.
+const hqpath = path.join(dir, "handlequeries.json");
+const handleQueries = withHandles && fs.existsSync(hqpath) ? JSON.parse(fs.readFileSync(hqpath)) : { ranges: [], positions: [] };
+const handleRanges = [], handlePositions = [];
+function refAssert(cond, msg) { if (!cond) throw new Error(`assert: ${msg}`); }
+// HandleCache.getHandles(start, end) (handlecache.ts:69-83): segment.start + offset of every position, raw (an
+// unallocated segment gives Handle.unallocated + offset). The reference method checks nothing itself: its callers do.
+// Every position passes getMaybeHandle's assert (permutationvector.ts:158) first, as it does on its way into the cache.
+// Two refusals are NOT reference behaviour but the batched call's validity rule (0 <= start <= end <= length), marked
+// `rule: true` in the answer: a reversed range and an empty range outside [0, length], for which the reference's loop
+// would run zero times and return [].
+function getHandles(client, start, end) {
+    const length = client.getLength();
+    if (!(start <= end)) throw Object.assign(new RangeError(`getHandles: [${start}, ${end}) ends before it starts`), { rule: true });
+    if (start === end && !(0 <= start && start <= length)) throw Object.assign(new RangeError("empty range outside the vector"), { rule: true });
+    const handles = [];
+    for (let pos = start; pos < end; pos++) {
+        refAssert(0 <= pos && pos < length, "getMaybeHandle: 0 <= pos && pos < this.getLength()");
+        const { segment, offset } = client.getContainingSegment(pos);
+        handles.push(segment.start + offset);
+    }
+    return handles;
+}
+// PermutationVector.handleToPosition(handle, localSeq) (permutationvector.ts:198-253)
+function handleToPosition(client, handle, localSeq = client.mergeTree.collabWindow.localSeq) {
+    refAssert(localSeq <= client.mergeTree.collabWindow.localSeq, "'localSeq' must be <= the last submitted op's");
+    let containingSegment, containingOffset;
+    client.mergeTree.walkAllSegments(client.mergeTree.root, (segment) => {
+        const { start, cachedLength } = segment;
+        if (!isHandleValid(start)) return true;
+        const end = start + cachedLength;
+        if (start <= handle && handle < end) {
+            containingSegment = segment;
+            containingOffset = handle - start;
+            return false;
+        }
+        return true;
+    });
+    refAssert(isHandleValid(containingSegment.start), "isHandleValid(containingSegment.start)");
+    return client.findReconnectionPostition(containingSegment, localSeq) + containingOffset;
+}
 const t0 = process.hrtime.bigint();
 const dumps = [], errs = {};
 for (let d = 0; d < ndocs; d++) {
@@ -741,6 +785,16 @@ for (let d = 0; d < ndocs; d++) {
                 const st = c.getStackContext(pos === null ? undefined : pos, [label])[label];
                 stackAnswers.push(st === undefined ? [] : st.items.map((m) => [segs.indexOf(m), m.refType]));
             }
+        }
+        for (const [qd, st, en] of handleQueries.ranges) {
+            if (qd !== d) continue;
+            try { handleRanges.push({ handles: getHandles(c, st, en) }); } catch (e) { handleRanges.push({ throws: String(e && e.message || e), rule: !!(e && e.rule) }); }
+        }
+        for (const [qd, handle, localSeq] of handleQueries.positions) {
+            if (qd !== d) continue;
+            try {
+                handlePositions.push({ pos: handleToPosition(c, handle, localSeq === null ? undefined : localSeq) });
+            } catch (e) { handlePositions.push({ throws: String(e && e.message || e) }); }
         }
         for (const [qd, id, before, offset] of relQueries) {
             if (qd !== d) continue;
@@ -846,6 +900,9 @@ if (withHandles) {
     const snap = {};
     for (const d of Object.keys(handleTables)) snap[d] = handleTables[d].snapshot();
     fs.writeFileSync(path.join(dir, "ref_handles.json"), JSON.stringify(snap));
+}
+if (handleQueries.ranges.length || handleQueries.positions.length) {
+    fs.writeFileSync(path.join(dir, "ref_hvec.json"), JSON.stringify({ ranges: handleRanges, positions: handlePositions }));
 }
 if (relQueries.length) fs.writeFileSync(path.join(dir, "ref_relpos.json"), JSON.stringify(relAnswers));
 if (markerQueries.tiles.length || markerQueries.stacks.length) {
