@@ -874,6 +874,138 @@ __global__ __launch_bounds__(WG) void k_handle_tables(Store<HT> st, int64_t m, c
     for (int64_t i = threadIdx.x; i < n && i < cap; i += WG) out[o + i] = t[i];
 }
 
+/* ---- batched delta-event reads (mt_engine_deltas_batch): the MT_DELTA_* streams (mt_oplog.h) of many documents, one
+ * wave per query; q.a = the cursor (a word index, < 0: invalid). The kernels read the DState and the logged words and
+ * nothing else: no Replica is built, so they keep no scratch in the document block (checked against Doc::dstate /
+ * Doc::dlog, which only add offsets), and a tiled document may be named by any number of queries of one launch;
+ * read_plan's successive launches for tiled documents are harmless.
+ *
+ * Event boundaries are found structurally, not by looking for MT_DELTA_END among all words. mt_oplog.h promises only
+ * that no position or length equals it, and the other words can: an ANNOTATE segment's property delta is
+ * (key << 16 | previous value) (Replica::prop_deltas), mt_kv.key is a full uint16 and the host interners hand out key
+ * ids up to 0xFFFE, so key 0x8000 with no previous value (0) is exactly 0x80000000; `seq` is the record's, which
+ * mt_engine_submit does not bound either. (`nd` is a count >= -1 and a REGEN op type is 0..2: those two cannot.) So a
+ * ballot on the terminator's value over every word would split such an event in two. What dhead / dseg / dtail and the
+ * emitters do fix is the shape: op, seq, then segments of (pos, len, nd) with nd delta words after it only in an
+ * ANNOTATE event with nd > 0, then MT_DELTA_END where the next `pos` would be, then nseg. Only `pos` slots are ever
+ * compared with MT_DELTA_END. In every event but ANNOTATE the pos slots are 3 words apart, so the wave tests 64 of
+ * them per pass (PAR); an ANNOTATE event chains through its nd counts. The serial form (!PAR) chains every event and
+ * lane 0 copies: the same words either way. */
+template <bool PAR>
+__device__ inline int64_t delta_event_end(const int32_t* log, int64_t i, int64_t n) {
+    /* the word after the nseg of the event at i, -1 when the n logged words cut it short */
+    if (i + 2 > n) return -1;
+    int64_t j = i + 2;
+    if (PAR && log[i] != MT_DELTA_ANNOTATE) {
+        for (;;) {
+            const int64_t x = j + 3 * (int64_t)(threadIdx.x & 63);
+            const uint64_t hit = __ballot(x < n && log[x] == MT_DELTA_END);
+            if (hit) {
+                const int64_t t = j + 3 * (int64_t)__builtin_ctzll(hit) + 2;
+                return t <= n ? t : -1;
+            }
+            j += 3 * 64;
+            if (j >= n) return -1;
+        }
+    }
+    while (j < n) {
+        if (log[j] == MT_DELTA_END) return j + 2 <= n ? j + 2 : -1;
+        if (j + 3 > n) return -1;
+        const int32_t nd = log[j + 2];
+        j += 3 + (log[i] == MT_DELTA_ANNOTATE && nd > 0 ? nd : 0);
+    }
+    return -1;
+}
+/* one query's window: the number of words it holds (written to out[0, that) when out != nullptr; never more than cap),
+ * *end = the next cursor, *rc = MT_E_ARG for an invalid cursor (an empty window, *end = from) */
+template <bool PAR>
+__device__ inline int64_t delta_window(const int32_t* log, int64_t n, int64_t from, int32_t kinds, int32_t* out,
+                                       int64_t cap, int64_t* end, int32_t* rc) {
+    const int lane = threadIdx.x & 63;
+    *rc = MT_OK;
+    *end = from;
+    bool ok = 0 <= from && from <= n;
+    if (ok && from != 0 && from != n) { /* an event boundary: the walk from word 0 lands on it */
+        int64_t i = 0;
+        while (i >= 0 && i < from) i = delta_event_end<PAR>(log, i, n);
+        ok = i == from;
+    }
+    if (!ok) {
+        *rc = MT_E_ARG;
+        return 0;
+    }
+    auto copy = [&](int64_t src, int64_t len, int64_t dst) {
+        if (!out) return;
+        if (PAR) {
+            for (int64_t k = lane; k < len && dst + k < cap; k += 64) out[dst + k] = log[src + k];
+        } else if (lane == 0) {
+            for (int64_t k = 0; k < len && dst + k < cap; k++) out[dst + k] = log[src + k];
+        }
+    };
+    if (kinds == (MT_DELTA_KINDS_SEQUENCE | MT_DELTA_KINDS_MAINTENANCE)) {
+        copy(from, n - from, 0);
+        *end = n;
+        return n - from;
+    }
+    /* whole events of one kind; neighbouring kept events are copied as one run */
+    const bool want_seq = kinds == MT_DELTA_KINDS_SEQUENCE;
+    int64_t i = from, total = 0, run = -1;
+    while (i < n) {
+        const int64_t t = delta_event_end<PAR>(log, i, n);
+        if (t < 0) break; /* the trailing event dcap cut short: left out, the next cursor is its start */
+        const bool keep = (log[i] >= 0) == want_seq;
+        if (keep && run < 0) run = i;
+        if (!keep && run >= 0) {
+            copy(run, i - run, total);
+            total += i - run;
+            run = -1;
+        }
+        i = t;
+    }
+    if (run >= 0) {
+        copy(run, i - run, total);
+        total += i - run;
+    }
+    *end = i;
+    return total;
+}
+/* the logged words of a document as the caller's engine counts them: min(n, dcap) with the caller's dcap, and never
+ * past this store's own log */
+template <class HT>
+__device__ inline int64_t delta_logged(const Doc<HT>& v, int32_t dcap) {
+    int64_t n = v.dstate()->n;
+    if (n > dcap) n = dcap;
+    if (n > v.caps.dcap) n = v.caps.dcap;
+    return n < 0 ? 0 : n;
+}
+/* size[slot] = the words of query i's window, end[slot] = its next cursor, emit[slot] = DState.n, status[slot] */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_delta_sizes(Store<HT> st, int64_t m, const ReadQ* qs, int32_t dcap,
+                                                   int32_t kinds, int64_t* size, int64_t* end, int64_t* emit,
+                                                   int32_t* status) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const Doc<HT> v = st.doc(q.doc);
+    int64_t e;
+    int32_t rc;
+    const int64_t n = delta_window<PAR>(v.dlog(), delta_logged(v, dcap), q.a, kinds, nullptr, 0, &e, &rc);
+    if (threadIdx.x == 0) size[q.slot] = n, end[q.slot] = e, emit[q.slot] = v.dstate()->n, status[q.slot] = rc;
+}
+/* query i's window into out[off[slot], off[slot + 1]) (the host's prefix sum of k_delta_sizes' sizes) and nowhere
+ * else */
+template <class HT, bool PAR>
+__global__ __launch_bounds__(WG) void k_deltas(Store<HT> st, int64_t m, const ReadQ* qs, int32_t dcap, int32_t kinds,
+                                              const int64_t* off, int32_t* out) {
+    if ((int64_t)blockIdx.x >= m) return;
+    const ReadQ q = qs[blockIdx.x];
+    const int64_t o = off[q.slot], cap = off[q.slot + 1] - o;
+    if (cap <= 0) return;
+    const Doc<HT> v = st.doc(q.doc);
+    int64_t e;
+    int32_t rc;
+    (void)delta_window<PAR>(v.dlog(), delta_logged(v, dcap), q.a, kinds, out + o, cap, &e, &rc);
+}
+
 /* every segment's handle in walkAllSegments order (the canonical dump's record order): out[2i] = row id,
  * out[2i+1] = its generation; *n = the segment count (writes at most cap pairs) */
 template <class HT>
@@ -1025,6 +1157,7 @@ struct mt_engine {
     bool summaries_parallel = true; /* k_summaries' writer (MT_VAR_SUMMARIES_PARALLEL) */
     bool tiles_parallel = true; /* k_find_tiles' / k_stacks' walk (MT_VAR_TILES_PARALLEL) */
     bool handles_parallel = true; /* k_handles' / k_handle_positions' walk (MT_VAR_HANDLES_PARALLEL) */
+    bool deltas_parallel = true; /* k_delta_sizes' / k_deltas' walk and copy (MT_VAR_DELTAS_PARALLEL) */
     DevBuf rq;                                   /* the batched reads' queries, results and text (mt_replay.hip) */
     hipStream_t run_stream = nullptr;
     /* mt_engine_submit_run: the copy stream, the second compute stream, and pinned staging buffers for pageable
@@ -1104,6 +1237,11 @@ struct ProfOps {
     int32_t (*handle_table_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int64_t* dsize);
     int32_t (*handle_tables)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, const int64_t* doff,
                              int32_t* dout);
+    /* the delta-event reads: dcap = the caller's engine's (a promoted document's engine logs more) */
+    int32_t (*delta_sizes)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t dcap, int32_t kinds,
+                           int64_t* dsize, int64_t* dend, int64_t* demit, int32_t* dstatus, bool par);
+    int32_t (*deltas)(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t dcap, int32_t kinds,
+                      const int64_t* doff, int32_t* dout, bool par);
 };
 /* each profile's table (host functions, defined in its mt_prof_*.hip) */
 const ProfOps* ops_small();
@@ -1302,10 +1440,31 @@ struct Launch {
         hipLaunchKernelGGL((k_handle_tables<HT>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, doff, dout);
         return launch_check(e, "k_handle_tables");
     }
+    static int32_t delta_sizes(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t dcap, int32_t kinds,
+                               int64_t* dsize, int64_t* dend, int64_t* demit, int32_t* dstatus, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_delta_sizes<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dcap,
+                               kinds, dsize, dend, demit, dstatus);
+        else
+            hipLaunchKernelGGL((k_delta_sizes<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dcap,
+                               kinds, dsize, dend, demit, dstatus);
+        return launch_check(e, "k_delta_sizes");
+    }
+    static int32_t deltas(mt_engine* e, hipStream_t s, int64_t m, const ReadQ* dq, int32_t dcap, int32_t kinds,
+                          const int64_t* doff, int32_t* dout, bool par) {
+        if (par)
+            hipLaunchKernelGGL((k_deltas<HT, true>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dcap, kinds,
+                               doff, dout);
+        else
+            hipLaunchKernelGGL((k_deltas<HT, false>), docs_grid(m), dim3(WG), 0, s, store_of<HT>(e), m, dq, dcap, kinds,
+                               doff, dout);
+        return launch_check(e, "k_deltas");
+    }
     static ProfOps table(int32_t (*replay)(mt_engine*)) {
         return ProfOps{init,   start_collab, replay, hdr,     digest,     dump,  length, text,       seg,
                        refpos, segids,       lengths, text_sizes, texts, segs,   dump_sizes, dumps,
                        summary_sizes, summaries, find_tiles, stack_sizes, stacks,
-                       handle_sizes, handles, handle_positions, handle_table_sizes, handle_tables};
+                       handle_sizes, handles, handle_positions, handle_table_sizes, handle_tables,
+                       delta_sizes, deltas};
     }
 };

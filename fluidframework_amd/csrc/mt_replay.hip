@@ -882,6 +882,10 @@ int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value) {
         if (value != 0 && value != 1) return MT_E_ARG;
         e->handles_parallel = value == 1;
         return MT_OK;
+    case MT_VAR_DELTAS_PARALLEL:
+        if (value != 0 && value != 1) return MT_E_ARG;
+        e->deltas_parallel = value == 1;
+        return MT_OK;
     default:
         return MT_E_ARG;
     }
@@ -1618,6 +1622,68 @@ int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap) {
     if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
     const DState* ds = doc_block(e, doc).dstate;
     return read_counted(e, ds, [&](const DState& st) { return std::min(st.n, dcap); }, ds + 1, 4, out, cap);
+}
+
+/* the batched form (mt_kernels.h k_delta_sizes / k_deltas): sizes, the prefix sum on the host, then the fill */
+int64_t mt_engine_deltas_batch(mt_engine* e, int64_t m, const int64_t* docs, const int64_t* from_words, int32_t kinds,
+                               int64_t* off_out, int64_t* end_out, int64_t* emitted_out, int32_t* status_out,
+                               int32_t* out, int64_t cap) {
+    if (!e || e->dcap <= 0 || m < 0 || cap < 0 || kinds <= 0 ||
+        (kinds & ~(MT_DELTA_KINDS_SEQUENCE | MT_DELTA_KINDS_MAINTENANCE)))
+        return -MT_E_ARG;
+    if (m == 0) return 0;
+    if (!off_out || !status_out) return -MT_E_ARG;
+    /* a cursor is a word index below dcap, an int32: one that is not is invalid like any negative one */
+    std::vector<int32_t> from;
+    if (from_words) {
+        from.resize((size_t)m);
+        for (int64_t i = 0; i < m; i++)
+            from[(size_t)i] = from_words[i] < 0 || from_words[i] > e->dcap ? -1 : (int32_t)from_words[i];
+    }
+    ReadPlan p;
+    int32_t rc = read_plan(e, m, docs, from_words ? from.data() : nullptr, nullptr, 0, nullptr, nullptr, p);
+    if (rc) return -rc;
+    if (hipSetDevice(e->device) != hipSuccess) return -MT_E_HIP;
+    /* the queries, their sizes, the offsets, the next cursors, the emitted counts, the statuses */
+    const size_t qb = up16(sizeof(ReadQ) * (size_t)m), sb = up16(8 * (size_t)m), ob = up16(8 * ((size_t)m + 1));
+    if ((rc = ensure(e, e->rq, qb + 3 * sb + ob + 4 * (size_t)m))) return -rc;
+    uint8_t* base = (uint8_t*)e->rq.p;
+    ReadQ* dq = (ReadQ*)base;
+    int64_t* dsize = (int64_t*)(base + qb);
+    int64_t* dend = (int64_t*)(base + qb + sb);
+    int64_t* demit = (int64_t*)(base + qb + 2 * sb);
+    int64_t* doff = (int64_t*)(base + qb + 3 * sb);
+    int32_t* dst = (int32_t*)(base + qb + 3 * sb + ob);
+    if (hipMemcpyAsync(dq, p.q.data(), sizeof(ReadQ) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    const int32_t dcap = e->dcap; /* the caller's engine's, as mt_engine_deltas */
+    const bool par = e->deltas_parallel;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->delta_sizes(x, s, n, q, dcap, kinds, dsize, dend, demit, dst, par);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(off_out + 1, dsize, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipMemcpyAsync(status_out, dst, 4 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        (end_out && hipMemcpyAsync(end_out, dend, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
+        (emitted_out &&
+         hipMemcpyAsync(emitted_out, demit, 8 * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess) ||
+        hipStreamSynchronize(e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    off_out[0] = 0;
+    for (int64_t i = 0; i < m; i++) off_out[i + 1] += off_out[i];
+    const int64_t total = off_out[m];
+    if (!out || total > cap || total == 0) return total; /* all or nothing */
+    if (ensure(e, e->tmp, 4 * (size_t)total)) return -MT_E_NOMEM;
+    int32_t* dout = (int32_t*)e->tmp.p;
+    if (hipMemcpyAsync(doff, off_out, 8 * ((size_t)m + 1), hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return -MT_E_HIP;
+    rc = read_launch(e, p, dq, [&](mt_engine* x, hipStream_t s, const ReadQ* q, int64_t n) {
+        return x->ops->deltas(x, s, n, q, dcap, kinds, doff, dout, par);
+    });
+    if (rc) return -rc;
+    if (hipMemcpyAsync(out, dout, 4 * (size_t)total, hipMemcpyDeviceToHost, e->stream) != hipSuccess) return -MT_E_HIP;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return -MT_E_HIP;
+    return total;
 }
 
 int32_t mt_engine_doc_error(mt_engine* e, int64_t doc, int32_t* err, int32_t* err_op) {

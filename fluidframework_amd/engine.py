@@ -46,6 +46,8 @@ MT_VAR_DUMPS_PARALLEL = 5
 MT_VAR_SUMMARIES_PARALLEL = 6
 MT_VAR_TILES_PARALLEL = 7
 MT_VAR_HANDLES_PARALLEL = 8
+MT_VAR_DELTAS_PARALLEL = 9
+DELTA_KINDS_SEQUENCE, DELTA_KINDS_MAINTENANCE = 1, 2  # MT_DELTA_KINDS_* (include/mt_engine.h)
 
 
 def lib() -> ctypes.CDLL:
@@ -104,6 +106,8 @@ def lib() -> ctypes.CDLL:
         L.mt_engine_ref_positions.argtypes = [vp, vp, vp]
         L.mt_engine_deltas.argtypes = [vp, i64, vp, i64]
         L.mt_engine_deltas.restype = i64
+        L.mt_engine_deltas_batch.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, i64]
+        L.mt_engine_deltas_batch.restype = i64
         L.mt_engine_resolve_remote_client_position.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(i32)]
         L.mt_engine_adjust_position.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(i32)]
         L.mt_engine_handle_to_position.argtypes = [vp, i64, i32, i32, ctypes.POINTER(i32)]
@@ -705,6 +709,37 @@ class Engine:
         buf = np.zeros(max(n, 1), np.int32)
         self.L.mt_engine_deltas(self.h, doc, _p(buf), n)
         return buf[:n]
+
+    def deltas_batch_raw(self, docs=None, from_words=None, kinds=DELTA_KINDS_SEQUENCE | DELTA_KINDS_MAINTENANCE):
+        """The delta streams of many documents in one call (mt_engine_deltas_batch): (off, words, end, emitted, status).
+        Query i's words are words[off[i]:off[i+1]]: with both kinds the logged words from the cursor from_words[i] (None:
+        0; a scalar is broadcast) on, verbatim; with one kind the whole events of that kind (oplog.filter_deltas states
+        the rules). end[i] is the next cursor, emitted[i] the words emitted since create / reset (> dcap: the log
+        saturated), status[i] 0 or MT_E_ARG for a cursor that is no event boundary (its window is empty). One size call
+        and one fill call."""
+        m, d, _, _ = self._queries(docs, None, None)
+        fw = None if from_words is None else np.ascontiguousarray(
+            np.broadcast_to(np.asarray(from_words, np.int64), (m,)))
+        off, end, emitted = np.zeros(m + 1, np.int64), np.zeros(m, np.int64), np.zeros(m, np.int64)
+        st = np.zeros(m, np.int32)
+
+        def call(out, cap):
+            n = self.L.mt_engine_deltas_batch(self.h, m, self._pn(d), self._pn(fw), kinds, _p(off), _p(end),
+                                              _p(emitted), _p(st), out, cap)
+            if n < 0:
+                raise EngineError(f"deltas_batch failed {n}", -n)
+            return n
+        n = call(None, 0)
+        buf = np.zeros(max(n, 1), np.int32)
+        if n and call(_p(buf), n) != n:  # nothing replays between the two calls
+            raise EngineError("deltas_batch size changed")
+        return off, buf[:n], end, emitted, st
+
+    def deltas_batch(self, docs=None, from_words=None, kinds=DELTA_KINDS_SEQUENCE | DELTA_KINDS_MAINTENANCE):
+        """deltas_batch_raw as a list of arrays, one per query (an invalid cursor's is empty; use deltas_batch_raw for
+        the next cursors and the statuses)."""
+        off, words, _, _, _ = self.deltas_batch_raw(docs, from_words, kinds)
+        return [words[off[i]:off[i + 1]] for i in range(len(off) - 1)]
 
     def ref_positions(self):
         """Per doc the number of local references, and (ndocs, rcap) LocalReference.toPosition() of each

@@ -102,6 +102,9 @@ export declare class Interner {
     knownKey(k: string): number;
 }
 
+/** event kinds of ReplayEngine.deltaEvents / addon.deltasBatch (MT_DELTA_KINDS_*) */
+export declare const DELTA_KINDS: { SEQUENCE: 1; MAINTENANCE: 2 };
+
 export declare function decodeDeltas(words: Int32Array, interner: Interner): DeltaEvent[];
 
 /** the canonical segment dump (include/mt_oplog.h) as segment objects; nameOf maps long client indices to ids */
@@ -144,6 +147,10 @@ export declare class ReplayEngine {
     handlesToPositions(queries: { doc: number; handle: number; localSeq?: number }[]): (number | undefined)[];
     /** HandleTable.snapshot() of every listed document (default: all) in one call (mt_engine_handle_tables) */
     handleTables(docs?: number[]): Int32Array[];
+    /** the decoded delta events of every listed document (default: all) in one call (mt_engine_deltas_batch): per
+     *  document what GpuClient.deltaEvents returns; kinds (a DELTA_KINDS mask, default both) leaves the other kind's
+     *  words on the device */
+    deltaEvents(docs?: number[], options?: { kinds?: number }): DeltaEvent[][];
     longIndex(name: string): number;
 }
 

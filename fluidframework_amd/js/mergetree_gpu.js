@@ -112,6 +112,7 @@ class Interner {
 }
 
 /* MergeTreeDeltaType / MergeTreeMaintenanceType names of the delta stream's op words (include/mt_oplog.h) */
+const DELTA_KINDS = { SEQUENCE: 1, MAINTENANCE: 2 }; // MT_DELTA_KINDS_* (include/mt_engine.h)
 const DELTA_OPS = { 0: "INSERT", 1: "REMOVE", 2: "ANNOTATE", 3: "REGEN", "-1": "APPEND", "-2": "SPLIT", "-3": "UNLINK" };
 
 /* Decode a document's delta-stream words (include/mt_oplog.h MT_DELTA_*) into the events a SharedString
@@ -496,6 +497,24 @@ class ReplayEngine {
         checkDocs(this, docs);
         const { tables, offsets } = addon.handleTables(this.h, docs);
         return Array.from({ length: offsets.length - 1 }, (_, i) => tables.subarray(offsets[i], offsets[i + 1]));
+    }
+
+    /* the "sequenceDelta" / "maintenance" events of every listed document (all by default) in one call
+     * (mt_engine_deltas_batch), decoded (decodeDeltas): per document what GpuClient.deltaEvents returns. kinds is a mask
+     * of DELTA_KINDS.SEQUENCE (INSERT / REMOVE / ANNOTATE / REGEN) and DELTA_KINDS.MAINTENANCE (APPEND / SPLIT /
+     * UNLINK), default both; with one kind the other's words stay on the device. A log that ran full (caps.dcap) throws
+     * with both kinds, as GpuClient.deltaEvents does; with one kind its whole events of that kind are returned. */
+    deltaEvents(docs, options = {}) {
+        this.flush();
+        checkDocs(this, docs);
+        const kinds = options.kinds === undefined ? DELTA_KINDS.SEQUENCE | DELTA_KINDS.MAINTENANCE : options.kinds;
+        const r = addon.deltasBatch(this.h, docs, undefined, kinds);
+        return Array.from(r.status, (_, i) => {
+            if (kinds === 3 && r.emitted[i] > r.end[i]) {
+                throw new Error("delta log full: the engine's caps.dcap is too small for this document's events");
+            }
+            return decodeDeltas(r.words.subarray(r.off[i], r.off[i + 1]), this.interner);
+        });
     }
 }
 
@@ -958,5 +977,5 @@ class GpuClient {
     deltaEvents() { return decodeDeltas(addon.deltas(this.read(), this.doc), this.engine.interner); }
 }
 
-module.exports = { ReplayEngine, GpuClient, GpuMergeTree, Interner, addon, OP, DEFAULT_CAPS, decodeDeltas, decodeDump,
+module.exports = { ReplayEngine, GpuClient, GpuMergeTree, Interner, addon, OP, DEFAULT_CAPS, DELTA_KINDS, decodeDeltas, decodeDump,
     ReferenceType, LocalClientId, UnassignedSequenceNumber };

@@ -936,6 +936,61 @@ static napi_value js_handle_tables(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* deltasBatch(h, docs?, fromWords?, kinds?) -> {off: number[], words: Int32Array, end: number[], emitted: number[],
+ * status: Int32Array}: the delta streams of many documents in one call (mt_engine_deltas_batch; docs undefined: every
+ * document). fromWords[i] (undefined: 0) is query i's cursor, a word index that is an event boundary; kinds is a mask
+ * of MT_DELTA_KINDS_SEQUENCE (1) and MT_DELTA_KINDS_MAINTENANCE (2), default both. Query i's words are words[off[i] ..
+ * off[i+1]); end[i] is the next cursor, emitted[i] the words emitted since create / reset (> caps.dcap: the log
+ * saturated, and with both kinds the window ends inside an event), status[i] MT_E_ARG for a cursor that is no event
+ * boundary. A size query and a fill. */
+static napi_value js_deltas_batch(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value argv[4];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    if (argc < 1) {
+        napi_throw_type_error(env, nullptr, "missing arguments");
+        return nullptr;
+    }
+    mt_engine* e = engine_of(env, argv[0]);
+    std::vector<int64_t> docs, from;
+    bool all = true, zero = true;
+    int32_t kinds = MT_DELTA_KINDS_SEQUENCE | MT_DELTA_KINDS_MAINTENANCE;
+    if (!e || (argc > 1 && !docs_of(env, argv[1], &docs, &all)) || (argc > 2 && !docs_of(env, argv[2], &from, &zero)) ||
+        (argc > 3 && !opt_undefined(env, argv[3]) && !i32_of(env, argv[3], &kinds)))
+        return nullptr;
+    const size_t m = all ? (size_t)mt_engine_ndocs(e) : docs.size();
+    if (!zero && from.size() != m) return throw_status(env, e, MT_E_ARG, "deltasBatch (array lengths)");
+    const int64_t* dp = all ? nullptr : docs.data();
+    const int64_t* fp = zero ? nullptr : from.data();
+    std::vector<int64_t> off(m + 1, 0), end(m + 1, 0), emitted(m + 1, 0);
+    std::vector<int32_t> st(m + 1, 0);
+    int64_t n = mt_engine_deltas_batch(e, (int64_t)m, dp, fp, kinds, off.data(), end.data(), emitted.data(), st.data(),
+                                       nullptr, 0);
+    if (n < 0) return throw_status(env, e, (int32_t)-n, "mt_engine_deltas_batch (engine created without caps.dcap?)");
+    std::vector<int32_t> buf((size_t)n + 1);
+    if (n > 0) {
+        int64_t n2 = mt_engine_deltas_batch(e, (int64_t)m, dp, fp, kinds, off.data(), end.data(), emitted.data(),
+                                            st.data(), buf.data(), n);
+        if (n2 != n) return throw_status(env, e, n2 < 0 ? (int32_t)-n2 : MT_E_ARG, "mt_engine_deltas_batch");
+    }
+    auto numbers = [&](const std::vector<int64_t>& v) -> napi_value { /* the first m entries as a number[] */
+        napi_value arr;
+        NAPI_OK(napi_create_array_with_length(env, m, &arr));
+        for (size_t i = 0; i < m; i++) NAPI_OK(napi_set_element(env, arr, (uint32_t)i, num(env, (double)v[i])));
+        return arr;
+    };
+    napi_value out, offs = offsets_of(env, off, m), w = i32_array(env, buf.data(), (size_t)n),
+                    s = i32_array(env, st.data(), m), en = numbers(end), em = numbers(emitted);
+    if (!offs || !w || !s || !en || !em) return nullptr;
+    NAPI_OK(napi_create_object(env, &out));
+    NAPI_OK(napi_set_named_property(env, out, "off", offs));
+    NAPI_OK(napi_set_named_property(env, out, "words", w));
+    NAPI_OK(napi_set_named_property(env, out, "end", en));
+    NAPI_OK(napi_set_named_property(env, out, "emitted", em));
+    NAPI_OK(napi_set_named_property(env, out, "status", s));
+    return out;
+}
+
 /* handleToPosition(h, doc, handle, localSeq) -> number */
 static napi_value js_handle_to_position(napi_env env, napi_callback_info info) {
     napi_value argv[4];
@@ -1034,7 +1089,7 @@ static napi_value init(napi_env env, napi_value exports) {
                {"dumps", js_dumps},         {"summaries", js_summaries},
                {"findTiles", js_find_tiles}, {"stackContexts", js_stack_contexts},
                {"getHandles", js_get_handles}, {"handlesToPositions", js_handles_to_positions},
-               {"handleTables", js_handle_tables}};
+               {"handleTables", js_handle_tables}, {"deltasBatch", js_deltas_batch}};
     for (auto& f : fns) {
         napi_value fn;
         NAPI_OK(napi_create_function(env, f.name, NAPI_AUTO_LENGTH, f.cb, nullptr, &fn));

@@ -195,6 +195,60 @@ def decode_deltas(words):
     return out
 
 
+def _delta_event_spans(w):
+    """[(start, end, op)] of the whole events of a word list and the start of a trailing event the list cuts short
+    (len(w) if there is none): decode_deltas' parse, which finds an event's end from its segments' nd counts and never
+    by looking for DELTA_END among the property-delta words (a (key << 16 | value) word can equal it)."""
+    n, i, spans = len(w), 0, []
+    while i < n:
+        if i + 2 > n:
+            return spans, i
+        op, j = w[i], i + 2
+        while True:
+            if j >= n:
+                return spans, i
+            if w[j] == DELTA_END:
+                break
+            if j + 3 > n:
+                return spans, i
+            nd = w[j + 2]
+            j += 3 + (nd if op == 2 and nd > 0 else 0)
+        if j + 2 > n:
+            return spans, i
+        spans.append((i, j + 2, op))
+        i = j + 2
+    return spans, n
+
+
+DELTA_KINDS_SEQUENCE, DELTA_KINDS_MAINTENANCE = 1, 2  # MT_DELTA_KINDS_* (include/mt_engine.h)
+
+
+def filter_deltas(words, kinds, from_word=0):
+    """What mt_engine_deltas_batch answers for one document whose logged words are `words` (include/mt_engine.h):
+    (kept words, end). `kinds` is a mask: DELTA_KINDS_SEQUENCE keeps the events with op >= 0 (INSERT, REMOVE, ANNOTATE,
+    REGEN: "sequenceDelta"), DELTA_KINDS_MAINTENANCE those with op < 0 (APPEND, SPLIT, UNLINK: "maintenance"). Both
+    bits: words[from_word:] verbatim, a cut-short last event included, and end = len(words). One bit: the whole events
+    of that kind from from_word on, each verbatim, without a trailing event the list cuts short; end is that event's
+    start, or len(words). from_word must be an event boundary (0, the word after an event's nseg, or len(words)):
+    anything else raises ValueError, as does kinds 0 or an unknown bit."""
+    if kinds not in (1, 2, 3):
+        raise ValueError(f"kinds {kinds}")
+    w = np.asarray(words, np.int64).reshape(-1).tolist()
+    n = len(w)
+    spans, tail = _delta_event_spans(w)
+    if from_word not in {0, n} | {e for _, e, _ in spans}:
+        raise ValueError(f"cursor {from_word} is not an event boundary")
+    if kinds == 3:
+        return w[from_word:], n
+    if from_word == n:
+        return [], n
+    out = []
+    for s, e, op in spans:
+        if s >= from_word and (op >= 0) == (kinds == DELTA_KINDS_SEQUENCE):
+            out += w[s:e]
+    return out, tail
+
+
 # values the engine derives from incr / consensus annotates (include/mt_oplog.h MT_VALUE_DERIVED ..): host interners
 # stay below VALUE_DERIVED; a dump writes each by its kind, its contents after the segment's pairs
 VALUE_DERIVED, VALUE_STRCAT0, VALUE_CONS0, VALUE_NAN = 0x7F00, 0x7F00, 0x7F80, 0x7FFF

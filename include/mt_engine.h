@@ -150,10 +150,14 @@ int32_t mt_engine_set_order(mt_engine* e, const int32_t* order);
  *     takes a pass of 64 rows at once (and writes a pass's handles together), 0 = the serial walk of the host core and
  *     the single call's leaf-per-pass search (a second device check, and the A/B baseline); takes effect at the next
  *     such call.
+ *   MT_VAR_DELTAS_PARALLEL (0 | 1): how mt_engine_deltas_batch finds event ends and copies: 1 = the wave tests 64
+ *     segment headers of an event at once and copies each run of kept events together, 0 = one lane walks segment by
+ *     segment and copies word by word (a second device check, and the A/B baseline); takes effect at the next such
+ *     call.
  * Takes effect at the next mt_engine_run / mt_engine_submit_run. */
 enum { MT_VAR_SMALL_WAVES = 1, MT_VAR_TILED_WIDE = 2, MT_VAR_CHUNK_DOCS = 3, MT_VAR_TEXTS_PACKED = 4,
        MT_VAR_DUMPS_PARALLEL = 5, MT_VAR_SUMMARIES_PARALLEL = 6, MT_VAR_TILES_PARALLEL = 7,
-       MT_VAR_HANDLES_PARALLEL = 8 };
+       MT_VAR_HANDLES_PARALLEL = 8, MT_VAR_DELTAS_PARALLEL = 9 };
 int32_t mt_engine_set_variant(mt_engine* e, int32_t key, int32_t value);
 
 /* Per-doc latched error code (MT_E_*) and index of the event that raised it (-1 if none). */
@@ -342,6 +346,32 @@ int64_t mt_engine_segment_ids(mt_engine* e, int64_t doc, int32_t* out, int64_t c
  * at most cap of them and returns how many are logged (<0 on error). */
 int32_t mt_engine_delta_state(mt_engine* e, int64_t* n_out, uint64_t* hash_out);
 int64_t mt_engine_deltas(mt_engine* e, int64_t doc, int32_t* out, int64_t cap);
+/* The delta streams of many documents in one call: what a host that forwards "sequenceDelta" (op >= 0 events:
+ * INSERT, REMOVE, ANNOTATE, REGEN) and "maintenance" (op < 0: APPEND, SPLIT, UNLINK) to its listeners reads after
+ * every replay (sequence.ts:136-150; MergeTreeMaintenanceType, mergeTreeDeltaCallback.ts:16-30), m queries, one wave
+ * each. The call contract is that of mt_engine_handle_tables / mt_engine_get_texts: docs == NULL = documents 0..m-1;
+ * documents may repeat, in any order; m == 0 returns 0 and touches nothing; an engine created without caps.dcap
+ * returns -MT_E_ARG; the return value is the total word count (<0: -MT_E_* for engine-level errors only); off_out[0..m]
+ * is always filled, query i's words are out[off_out[i] .. off_out[i+1]); `out` is written only when the total fits cap
+ * (all or nothing); out == NULL is the size query. Promoted documents answer from their engines; as in
+ * mt_engine_deltas the logged length is min(n, dcap) with the dcap of the engine the caller holds.
+ *   from_words[i] (NULL: 0) is a cursor: a word index into the document's log that is an event boundary: word 0, the
+ *     word after any event's nseg, or the logged end. Any other value (negative, past the logged end, inside an event)
+ *     gives status_out[i] = MT_E_ARG and an empty window, and does not fail the call.
+ *   kinds is a mask of MT_DELTA_KINDS_*; 0 or an unknown bit returns -MT_E_ARG. Both bits: the window is the words
+ *     [from, logged end) verbatim, mt_engine_deltas' tail, a last event cut short by dcap included. One bit: the whole
+ *     events of that kind from the cursor on, in order, each verbatim from its op word through its nseg word; a
+ *     trailing event cut short by dcap is left out.
+ *   end_out[i] (optional) is the next cursor: the logged end, or with one bit set the start of the cut-short trailing
+ *     event if the walk met one.
+ *   emitted_out[i] (optional) is the words emitted since create / reset (mt_engine_delta_state's n): emitted > dcap
+ *     tells the caller the log saturated.
+ *   status_out is required. */
+#define MT_DELTA_KINDS_SEQUENCE 1    /* op >= 0: INSERT, REMOVE, ANNOTATE, REGEN */
+#define MT_DELTA_KINDS_MAINTENANCE 2 /* op <  0: APPEND, SPLIT, UNLINK */
+int64_t mt_engine_deltas_batch(mt_engine* e, int64_t m, const int64_t* docs, const int64_t* from_words, int32_t kinds,
+                               int64_t* off_out, int64_t* end_out, int64_t* emitted_out, int32_t* status_out,
+                               int32_t* out, int64_t cap);
 /* Local references (MT_OP_REF records; engines created with caps.rcap > 0): per doc the number of
  * references (nref_out[d]) and, for reference i, LocalReference.toPosition() (localReference.ts:62-68:
  * Client.getPosition(segment) + getOffset(), -1 when detached) at pos_out[d * rcap + i]; the row length is
